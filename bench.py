@@ -10,8 +10,15 @@ called as plain `python bench.py --gpus N` -- re-executed under it by this scrip
 torch.distributed.launch, run_r2r/main.bash:53) each rank owns its own batch (weak scaling = the reference's per-rank
 batch semantics, loader.py:127-164; `--scaling strong` splits the global batch of 32 instead) and the step ends when
 the RCCL gradient mean has completed.  Workload at N=1: BASELINE.json configs[1] (B=32, 36 views x 768-d, 80 tokens, 16 nodes,
-bf16).  Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed) and `cpu_baseline` (the CPU
-oracle timed on the host cores on a bounded sample).
+bf16).  Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line; the legs
+measured after the timed region -- `roofline` (dominant kernel, HIP-event timed), `optimizer` (fused AdamW), `cpu_baseline`
+(the CPU oracle timed on the host cores on a bounded sample) and, at N > 1, `comm` (exposed communication time of both
+transports) -- run only with --full and are null otherwise.
+
+    python bench.py --steps K --warmup W --dump-outputs DIR
+
+writes what the last timed step computed as DIR/*.npy (see dump_outputs): same arguments, same inputs, so two builds can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -150,6 +157,38 @@ def env_overrides():
     return out
 
 
+GRAD_SAMPLE = 1 << 22          # 16 MB of fp32 gradient values; all files together stay far below 64 MB
+
+
+def dump_outputs(out_dir, step, model):
+    """What a caller of the timed step receives after its last step, as float32 / float64 .npy files in out_dir:
+    loss [1]; global_logits [n_sel] (the logits of the selectable nodes -- gmap_masks and not visited -- in row-major order;
+    the others are -inf by definition, and the masks are inputs, so n_sel is fixed); grad_norms [n] (float64 L2 norm of every
+    trainable parameter's gradient, named_parameters order); grad_sample [GRAD_SAMPLE] (gradient values at fixed positions
+    drawn uniformly, seed 0, over the concatenated trainable parameters -- the whole arena is ~560 MB, and the padding
+    between tensors is not part of any output)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    parts = getattr(step, "parts", [step])                 # MicroBatchedStep: one PlannerStep per micro-batch, batch order
+    grads = [p.grad for _, p in model.named_parameters() if p.grad is not None]
+    base, esz = model.flat_grads.data_ptr(), model.flat_grads.element_size()
+    sizes = torch.tensor([g.numel() for g in grads], dtype=torch.int64)
+    offs = torch.tensor([(g.data_ptr() - base) // esz for g in grads], dtype=torch.int64)
+    ends = sizes.cumsum(0)
+    pos = torch.randint(0, int(ends[-1]), (GRAD_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    k = torch.searchsorted(ends, pos, right=True)
+    idx = (offs[k] + pos - (ends[k] - sizes[k])).to(model.flat_grads.device)
+    arrays = {
+        "loss": sum(p.loss for p in parts).float(),
+        "global_logits": torch.cat([p.logits[p.inp["gmask"] & ~p.inp["visited"]] for p in parts]).float(),
+        "grad_norms": torch.stack([g.double().norm() for g in grads]),
+        "grad_sample": model.flat_grads[idx].float(),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+
+
 class LineWatchdog:
     """`value` is measured when the timed region ends; what follows at N > 1 (the exposed-communication legs, the SECOND communicator of
     the transport comparison, the teardown) is reported extras made of collectives -- and a first contact with RCCL on hardware the builder
@@ -238,6 +277,13 @@ def main():
                          "offers (the side streams of PlannerStep are created at the lowest either way)")
     ap.add_argument("--same-device", action="store_true",
                     help="TEST ONLY: every rank uses cuda:0 (needs --dist-backend gloo; RCCL refuses duplicate devices)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs after the timed region: roofline (per-kernel HIP-event timing), optimizer, "
+                         "cpu_baseline and, at N > 1, the communication legs (--no-roofline / --no-optimizer / --no-cpu-baseline / "
+                         "--no-comm-compare leave single legs out).  Off: the line holds the timed region only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, logits, gradient sample and per-tensor norms) as "
+                         "DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.comm_dtype == "auto":
         args.comm_dtype = "bf16" if args.dtype == "bf16" else "fp32"
@@ -373,6 +419,8 @@ def main():
         elapsed = float(t.item())
     loss = float(step.loss.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, model)
 
     def make_out(comm_info, roofline, optimizer, gemm_table):
         """the ONE JSON line (rank 0); a function since round 6 so that the watchdog of the post-metric communication legs can print it too"""
@@ -475,7 +523,7 @@ def main():
         if os.environ.get("ETP_BENCH_TEST_HANG") == str(rank):      # TEST ONLY: this rank never reaches the legs' collectives
             time.sleep(10 * leg_timeout)
 
-    if world > 1 and reducer is not None:
+    if world > 1 and reducer is not None and args.full:
         esz = 2 if args.comm_dtype == "bf16" else 4
         dense = sum(e - s0 for s0, e in reducer.ranges)
         sparse_b = (w["B"] * w["L"]) * (reducer.sparse[2] * esz + 8) if reducer.sparse is not None else 0
@@ -509,7 +557,7 @@ def main():
     # kernel with the step replayed on ONE stream (nothing else resident).  VERDICT r2 weak #5: round 2 printed only the latter.
     roofline, gemm_table = None, []
     peak_tf = PEAK_BF16_TFLOPS if args.dtype == "bf16" else 157.3
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         L = _lib.lib()
 
         def prof_steps(st, nprof=3):
@@ -631,7 +679,7 @@ def main():
     out = None
     # ---- optimizer leg (reported separately): fused AdamW closing the step on device ----
     optimizer = None
-    if rank == 0 and not args.no_optimizer:
+    if rank == 0 and args.full and not args.no_optimizer:
         from etpnav_amd.optim import FusedAdamW
         opt = FusedAdamW(model, lr=1e-5)                          # ss_trainer_ETP.py:213 torch.optim.AdamW semantics
         eng = model._engine
@@ -673,7 +721,7 @@ def main():
                                                     "because the optimizer kernel already wrote the shadows and zeroed the arena"}
     if rank == 0:
         out = make_out(comm_info, roofline, optimizer, gemm_table)
-        if world == 1 and not args.no_cpu_baseline and args.workload != "sap":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload != "sap":
             out["cpu_baseline"] = cpu_baseline(w, dict(image_feat_size=w["image_feat_size"]), train=args.mode == "train")
         else:
             out["cpu_baseline"] = None

@@ -1,8 +1,7 @@
 """Import the *real* reference planner (/root/reference) on CPU.  TEST INFRASTRUCTURE ONLY.
 
 Only usable in the build container (the GPU box has no /root/reference); used
-by ``oracle/make_golden.py`` to generate the fixtures in ``tests/golden/`` and by
-``tests/test_oracle_vs_reference.py`` (skipped when the reference is absent).
+by ``oracle/make_golden.py`` and ``oracle/make_golden_refcheck.py`` to generate the fixtures in ``tests/golden/``.
 Follows SURVEY.md Appendix D: stub packages so ``vilmodel_cmt.py`` imports without
 habitat, replace ``BertPreTrainedModel.init_weights`` (transformers-5 drift).  No
 reference file is copied or modified.

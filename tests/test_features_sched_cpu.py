@@ -1,6 +1,7 @@
 """SURVEY.md §8f N4 remainders on the CPU: the view-feature store (dataset.py:375-388) and the warm-up-linear learning-rate
 schedule (optim/sched.py:17-30)."""
 import importlib.util
+import json
 import os
 
 import numpy as np
@@ -9,8 +10,6 @@ import torch
 
 from etpnav_amd import features as ft
 from etpnav_amd.optim import warmup_linear, get_lr_sched, WarmupLinearLR
-
-REF_SCHED = "/root/reference/pretrain_src/pretrain_src/optim/sched.py"
 
 
 def _store(tmp_path, n=7, V=36, Fi=16, Fd=8, suffix=".etpf"):
@@ -166,13 +165,13 @@ def test_warmup_linear_schedule_matches_the_reference_function():
         assert warmup_linear(s, w, t) == pytest.approx(v)
     assert get_lr_sched(0, 5e-5, 100, 1000) == 1e-8 and get_lr_sched(1000, 5e-5, 100, 1000) == 1e-8      # floor (sched.py:28-29)
     assert get_lr_sched(50, 5e-5, 100, 1000) == pytest.approx(2.5e-5)
-    if os.path.exists(REF_SCHED):
-        spec = importlib.util.spec_from_file_location("ref_sched", REF_SCHED)
-        ref = importlib.util.module_from_spec(spec); spec.loader.exec_module(ref)
-        class O: learning_rate = 5e-5; warmup_steps = 100; num_train_steps = 1000
-        for s in range(0, 1300, 37):
-            assert get_lr_sched(s, 5e-5, 100, 1000) == ref.get_lr_sched(s, O)
-            assert warmup_linear(s, 100, 1000) == ref.warmup_linear(s, 100, 1000)
+    # the reference's own functions on the same arguments (tests/golden/refcheck.json, generator oracle/make_golden_refcheck.py)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refcheck.json")) as f:
+        ref = json.load(f)["sched"]
+    assert ref["steps"] == list(range(0, 1300, 37))
+    for s, lr, wl in zip(ref["steps"], ref["get_lr_sched"], ref["warmup_linear"]):
+        assert get_lr_sched(s, 5e-5, 100, 1000) == lr
+        assert warmup_linear(s, 100, 1000) == wl
 
     class Opt: lr = 0.0
     o = Opt()

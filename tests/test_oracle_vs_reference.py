@@ -1,114 +1,111 @@
-"""Direct oracle-vs-reference check; only runs where /root/reference exists (build container)."""
+"""Oracle against outputs of the REAL reference stored under tests/golden/refcheck* (generator oracle/make_golden_refcheck.py,
+run where the reference exists)."""
+import json
+import os
+
+import numpy as np
 import pytest
 import torch
 
 from oracle import planner_oracle as po
-from oracle import ref_harness as rh
+from oracle import make_golden_refcheck as mr
 
-pytestmark = pytest.mark.skipif(not rh.reference_available(), reason="reference not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _refcheck():
+    with open(os.path.join(GOLDEN, "refcheck.json")) as f:
+        return json.load(f)
 
 
 def test_oracle_equals_reference_small():
-    cfg = po.PlannerConfig.r2r()
-    P = po.init_params(cfg, seed=3)
-    model = rh.build_reference_model(cfg, P)
-    batch = po.make_batch(cfg, B=2, L=10, V=13, G=6, seed=7, ragged=True)
-    ro, rg = rh.reference_step(model, batch)
+    """Every gradient as strided samples (abs 2e-5, as every element was held to) plus its abs-max and L2, which an elementwise
+    2e-5 bound implies to within 2e-5 and 2e-5 * sqrt(numel)."""
+    z = np.load(os.path.join(GOLDEN, "refcheck_step.npz"))
+    cfg, P, batch = mr.step_case()
     oo, og = po.step_with_grads(P, cfg, batch)
-    assert abs(float(ro["loss"] - oo["loss"])) < 1e-5
-    fin = torch.isfinite(ro["global_logits"])
-    assert float((ro["global_logits"][fin] - oo["global_logits"][fin]).abs().max()) < 2e-5
-    for k in rg:
-        assert float((rg[k] - og[k]).abs().max()) < 2e-5, k
+    assert abs(float(z["out.loss"]) - float(oo["loss"])) < 1e-5
+    ref = torch.from_numpy(z["out.global_logits"])
+    fin = torch.isfinite(ref)
+    assert torch.equal(torch.isfinite(oo["global_logits"]), fin)
+    assert float((ref[fin] - oo["global_logits"][fin]).abs().max()) < 2e-5
+    names = [k[4:] for k in z.files if k.startswith("gfp.")]
+    assert sorted(names) == sorted(og), "gradient set differs from the reference's"
+    for k in names:
+        g = og[k].detach().double().reshape(-1)
+        smp = torch.from_numpy(z[f"gsm.{k}"]).double()
+        assert float((g[torch.from_numpy(mr.sample_idx(g.numel()))] - smp).abs().max()) < 2e-5, k
+        fp = z[f"gfp.{k}"]
+        assert abs(float(g.abs().max()) - fp[1]) < 2e-5, k
+        assert abs(float(g.norm()) - fp[2]) < 2e-5 * g.numel() ** 0.5, k
 
 
 def test_saved_pretraining_checkpoint_loads_strictly_into_the_real_model():
     """etpnav_amd.checkpoint.pretrain_state_dict writes exactly the key set of the reference pre-training model
-    (utils/save.py:23-46): the REAL GlocalTextPathCMTPreTraining loads it with strict=True and then reproduces the
-    planner's own parameters."""
-    from oracle import ref_pretrain_harness as rp
+    (utils/save.py:23-46): what a strict load into the REAL GlocalTextPathCMTPreTraining checks -- the same keys, the same
+    shapes (the real model's state dict is stored in tests/golden/refcheck.json) -- and the loaded model then reproduces the
+    planner's own parameters: every value as given, and the tensors the real model ties (decoder = word embeddings) equal."""
     from etpnav_amd import checkpoint as ck
     from etpnav_amd.planner import GlocalTextPathNavCMT
+    ref = _refcheck()["pretrain_state_dict"]
     cfg = po.PlannerConfig.r2r(vocab_size=512, num_l_layers=1, num_pano_layers=1, num_x_layers=1, use_lang2visn_attn=True)
     P = po.init_params(cfg, seed=2)
     m = GlocalTextPathNavCMT(cfg.to_dict(), dtype=torch.float32, device="cpu")
     m.load_state_dict(P, strict=True)
-    real = rp.build_pretrain_model(cfg, po.init_params(cfg, seed=5))          # different weights before loading
-    missing, unexpected = real.load_state_dict(ck.pretrain_state_dict(m), strict=True)
-    assert not missing and not unexpected
-    got = {k: v for k, v in real.state_dict().items()}
+    got = ck.pretrain_state_dict(m)
+    want = {k: tuple(shape) for k, shape in ref["keys"]}
+    assert not set(want) - set(got) and not set(got) - set(want)          # missing, unexpected
+    assert {k: tuple(v.shape) for k, v in got.items()} == want
     for k, v in P.items():
         name = k if k.startswith(("mlm_head.", "global_sap_head.")) else "bert." + k
         assert torch.equal(got[name], v), k
-    assert got["mlm_head.predictions.decoder.weight"].data_ptr() == got["bert.embeddings.word_embeddings.weight"].data_ptr()
+    assert ["bert.embeddings.word_embeddings.weight", "mlm_head.predictions.decoder.weight"] in [sorted(t) for t in ref["tied"]]
+    for tied in ref["tied"]:
+        assert all(torch.equal(got[tied[0]], got[k]) for k in tied[1:]), tied
 
 
 @pytest.mark.parametrize("seed", list(range(30, 42)))
 def test_graph_assembly_randomised_against_the_real_classes(seed):
     """Beyond the committed golden episodes: random rollouts through the REAL GraphMap and through GraphMapLite must pack
-    identically, and the oracle's assembly must equal the trainer's REAL _nav_gmap_variable on them."""
-    import numpy as np
+    identically, and the oracle's assembly must equal the trainer's REAL _nav_gmap_variable on them (the real side's packed
+    episodes and outputs stored in tests/golden/refcheck_graph.npz)."""
     from oracle import graph_oracle as go
-    from oracle.make_golden_graph import load_reference_graph_utils, reference_batch_outputs
     from etpnav_amd.graph_inputs import GraphMapLite, pack_episode
-    gu = load_reference_graph_utils()
-    steps = 2 + seed % 9
-    merge = bool(seed % 2)
-    real = go.simulate(gu.GraphMap, seed, steps, merge_ghost=merge)
+    z = np.load(os.path.join(GOLDEN, "refcheck_graph.npz"))
+    a = {k: z[f"s{seed}/{k}"] for k in ("n_nodes", "n_ghost", "cur_node", "node_pos", "node_step", "adj", "ghost_pos",
+                                         "ghost_front_ptr", "ghost_front_idx", "gmap_step_ids", "gmap_visited_masks",
+                                         "gmap_pos_fts", "gmap_pair_dists")}
+    steps, merge = mr.graph_case(seed)
     lite = go.simulate(GraphMapLite, seed, steps, merge_ghost=merge)
-    a = pack_episode(real[0], real[1], real[2], real[3])
     b = pack_episode(lite[0], lite[1], lite[2], lite[3])
     assert a["n_nodes"] == b["n_nodes"] and a["n_ghost"] == b["n_ghost"] and a["cur_node"] == b["cur_node"]
     for k in ("node_pos", "node_step", "adj", "ghost_pos"):
-        assert np.allclose(a[k], b[k], atol=1e-12), k
-    assert a["ghost_fronts"] == b["ghost_fronts"]
-    ref = reference_batch_outputs(gu, [real[0]], [real[1]], [real[2]], [real[3]])
-    L = 1 + a["n_nodes"] + a["n_ghost"]
+        assert a[k].shape == np.asarray(b[k]).shape and np.allclose(a[k], b[k], atol=1e-12), k
+    ptr, idx = a["ghost_front_ptr"], a["ghost_front_idx"]
+    assert [idx[ptr[i]:ptr[i + 1]].tolist() for i in range(len(ptr) - 1)] == b["ghost_fronts"]
+    L = 1 + b["n_nodes"] + b["n_ghost"]
     got = go.assemble(b, G=L)
-    assert np.array_equal(got["gmap_step_ids"], ref["gmap_step_ids"][0].numpy())
-    assert np.array_equal(got["gmap_visited_masks"], ref["gmap_visited_masks"][0].numpy())
-    assert np.abs(got["gmap_pos_fts"] - ref["gmap_pos_fts"][0].numpy()).max() < 2e-6
-    assert np.abs(got["gmap_pair_dists"] - ref["gmap_pair_dists"][0].numpy()).max() < 2e-6
+    assert np.array_equal(got["gmap_step_ids"], a["gmap_step_ids"])
+    assert np.array_equal(got["gmap_visited_masks"], a["gmap_visited_masks"])
+    assert np.abs(got["gmap_pos_fts"] - a["gmap_pos_fts"]).max() < 2e-6
+    assert np.abs(got["gmap_pair_dists"] - a["gmap_pair_dists"]).max() < 2e-6
 
 
 @pytest.mark.parametrize("seed", [3, 4, 5, 6])
 def test_graph_map_lite_with_real_positions_and_ghost_jitter_against_the_real_class(seed):
     """The two GraphMap options the rollout driver above leaves off: has_real_pos (training keeps the simulator's positions of the
     candidates per ghost, graph_utils.py:213-214,225-226,236-237) and ghost_aug (position jitter from np.random, :245-252).  Both
-    classes are driven with the same candidates and the same numpy seed; every dict of the graph must agree."""
-    import numpy as np
-    from oracle.make_golden_graph import load_reference_graph_utils
+    classes are driven with the same candidates and the same numpy seed; every dict of the graph must agree (the real class's
+    state stored in tests/golden/refcheck.json)."""
     from etpnav_amd.graph_inputs import GraphMapLite
-    gu = load_reference_graph_utils()
-    out = []
-    for cls in (gu.GraphMap, GraphMapLite):
-        rng = np.random.RandomState(seed)
-        np.random.seed(1000 + seed)                          # the jitter draws from the global generator in both classes
-        g = cls(True, 0.5, bool(seed % 2), 0.3)              # has_real_pos, loc_noise, merge_ghost, ghost_aug
-        pos, heading, prev = np.array([0.3, 0.2, -0.4]), 1.0, None
-        for k in range(6):
-            n = rng.randint(2, 6)
-            cur_vp, cand_vp, cand_pos = g.identify_node(pos, heading, list(rng.uniform(0, 6.28, n)), list(rng.uniform(0.3, 2.0, n)))
-            real = [p + rng.normal(0, 0.05, 3) for p in cand_pos]
-            g.update_graph(prev, k + 1, cur_vp, pos, float(k), cand_vp, cand_pos, [float(10 * k + i) for i in range(n)], real)
-            prev = cur_vp
-            if k == 5:
-                break        # compare right after an update (the reference leaves a deleted ghost in ghost_aug_pos until the next one)
-            ghosts = list(g.ghost_pos.keys())
-            gv = ghosts[rng.randint(len(ghosts))]
-            pos, heading = np.array(g.ghost_real_pos[gv][0], dtype=np.float64), rng.uniform(0, 6.28)
-            g.delete_ghost(gv)
-        out.append(g)
-    a, b = out
-    edges_a = {tuple(sorted((u, v))): w for u, v, w in a.graph_nx.edges(data="weight")}
-    assert edges_a.keys() == b.edges.keys() and all(abs(edges_a[k] - b.edges[k]) < 1e-12 for k in edges_a)
-    assert list(a.node_pos) == list(b.node_pos) and a.node_stepId == b.node_stepId and a.ghost_cnt == b.ghost_cnt
-    for name in ("ghost_mean_pos", "ghost_aug_pos"):
-        da, db = getattr(a, name), getattr(b, name)
-        assert list(da) == list(db), name
-        assert all(np.allclose(da[k], db[k], atol=1e-12) for k in da), name
-    for name in ("ghost_pos", "ghost_real_pos"):
-        da, db = getattr(a, name), getattr(b, name)
-        assert list(da) == list(db) and all(np.allclose(np.asarray(da[k]), np.asarray(db[k]), atol=1e-12) for k in da), name
-    assert a.ghost_fronts == b.ghost_fronts
-    assert {k: (float(v[0]), v[1]) for k, v in a.ghost_embeds.items()} == {k: (float(v[0]), v[1]) for k, v in b.ghost_embeds.items()}
+    a = _refcheck()["ghost_aug_drive"][str(seed)]                          # the REAL class after the same drive
+    b = json.loads(json.dumps(mr.graph_state_after_ghost_aug_drive(GraphMapLite, seed)))
+    edges_a, edges_b = ({(u, v): w for u, v, w in x["edges"]} for x in (a, b))
+    assert edges_a.keys() == edges_b.keys() and all(abs(edges_a[k] - edges_b[k]) < 1e-12 for k in edges_a)
+    assert a["node_pos"] == b["node_pos"] and dict(a["node_stepId"]) == dict(b["node_stepId"]) and a["ghost_cnt"] == b["ghost_cnt"]
+    for name in ("ghost_mean_pos", "ghost_aug_pos", "ghost_pos", "ghost_real_pos"):
+        da, db = a[name], b[name]
+        assert [k for k, _ in da] == [k for k, _ in db], name
+        assert all(np.allclose(np.asarray(va), np.asarray(vb), atol=1e-12) for (_, va), (_, vb) in zip(da, db)), name
+    assert dict((k, v) for k, v in a["ghost_fronts"]) == dict((k, v) for k, v in b["ghost_fronts"])
+    assert {k: (e, c) for k, e, c in a["ghost_embeds"]} == {k: (e, c) for k, e, c in b["ghost_embeds"]}

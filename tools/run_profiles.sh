@@ -33,9 +33,9 @@ rm -rf $O/ps
 $T python tools/gemm_phase_probe.py > $O/gemm_phases.txt 2> $O/gemm_phases.err
 [ -n "$SKIP_CHAIN" ] || $T python tools/chain_waits.py --steps 24 --out $O/chain_waits.txt > /dev/null 2> $O/chain_waits.err
 # 6. the bench line (reads the two files copied into profiles/ above) and the other workloads
-$T python bench.py > $O/bench.json 2> $O/bench.err
-for wl in c4 c5 sap; do $T python bench.py --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err; done
-$T python bench.py --dtype fp32 --no-cpu-baseline > $O/bench_fp32.json 2> $O/bench_fp32.err
+$T python bench.py --full > $O/bench.json 2> $O/bench.err
+for wl in c4 c5 sap; do $T python bench.py --full --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err; done
+$T python bench.py --full --dtype fp32 --no-cpu-baseline > $O/bench_fp32.json 2> $O/bench_fp32.err
 for f in bench bench_c4 bench_c5 bench_sap bench_fp32; do python - <<PY
 import json
 try:
