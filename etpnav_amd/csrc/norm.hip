@@ -333,13 +333,14 @@ int ln_fwd_s(int dtype, const float* x, const float* gamma, const float* beta, f
 }
 // number of workgroups ln_bwd_s launches for M rows (= slabs of the two-stage reduction): every wave gets the same number
 // of rows, at most LN_BWD_MAX_BLOCKS blocks (one row per wavefront up to 4096 rows: 640 blocks at M = 2560; round 4, was 512 / two rows per wavefront)
+// The LNBWD_GRID switch is clamped to [1, LN_BWD_MAX_BLOCKS]: a larger cap would launch more blocks than ln_bwd_part_bytes has slabs for.
 static int ln_bwd_blocks(int M) {
   const int groups = (M + 3) / 4;
-  const int cap = std::max(1, opt_int(OPT_LNBWD_GRID, LN_BWD_MAX_BLOCKS));
+  const int cap = std::min(LN_BWD_MAX_BLOCKS, std::max(1, opt_int(OPT_LNBWD_GRID, LN_BWD_MAX_BLOCKS)));
   const int rounds = (groups + cap - 1) / cap;
   return (groups + rounds - 1) / rounds;
 }
-size_t ln_bwd_part_bytes(int M, int H) { return (size_t)std::min(ln_bwd_blocks(M), LN_BWD_MAX_BLOCKS) * 2 * H * sizeof(float); }
+size_t ln_bwd_part_bytes(int M, int H) { return (size_t)ln_bwd_blocks(M) * 2 * H * sizeof(float); }
 
 int ln_bwd_s(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add, float* dx,
              void* dxt, float* dgamma, float* dbeta, int M, int H, hipStream_t st, Drop drop, float* part) {

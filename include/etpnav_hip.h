@@ -167,7 +167,10 @@ int etp_ln_stream_bwd_stage1(int dtype, const float* dy, const float* x, const f
                              float* dx, void* dx_lp, float* dgamma, float* dbeta, float* part, int M, int H, etp_stream_t stream);
 int etp_ln_part_reduce(const float* part, int M, int H, float* dgamma, float* dbeta, etp_stream_t reduce_stream);
 
-/* BertEmbeddings.forward vilmodel_cmt.py:62-77 (eval): y = LN(word[id] + pos[l] + type[0]). */
+/* BertEmbeddings.forward vilmodel_cmt.py:62-77 (eval): y = LN(word[id] + pos[l] + type[0]).
+ * Forward: y, y_lp (may be NULL) and stats are OVERWRITTEN.  Backward: the parameter gradients dword / dpos / dtype0 / dgamma /
+ * dbeta are ACCUMULATED (+=) into what the caller passes (zero them for a fresh gradient); the padding row 0 of dword is not
+ * touched. */
 int etp_text_embed_fwd(int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0,
                        const float* gamma, const float* beta, float* y, void* y_lp, float* stats, int B, int L, int H, float eps,
                        etp_stream_t stream);
@@ -178,14 +181,17 @@ int etp_text_embed_bwd(int dtype, const float* dy, const int64_t* ids, const flo
 /* Panorama view-embedding fuse, forward_panorama vilmodel_cmt.py:695-711:
  *   y = LN(LN_i(a) + LN_d(d) + LN_l(loc.Wl^T+bl) + nav_emb[nav] + type_emb[1]); a,d (dtype T) = MFMA projections of rgb/depth.
  * params / grads: 12 fp32 pointers in the order g_img,b_img,g_dep,b_dep,w_loc,bias_loc,g_loc,b_loc,nav_emb,type1,g_out,b_out.
- * stats: [M,8]; y / dy fp32; da, dd in dtype T. */
+ * stats: [M,8]; y / dy fp32; da, dd in dtype T.  d (and dd) may be NULL: no depth branch, stats columns 2-3 are not written
+ * and grads[2] / grads[3] (g_dep, b_dep) are left untouched.
+ * Backward: the twelve parameter gradients are ACCUMULATED (+=); the row outputs da / dd are OVERWRITTEN. */
 int etp_pano_embed_fwd(int dtype, const void* a, const void* d, const float* loc, const int64_t* nav,
                        const float* const* params, float* y, float* stats, int M, int H, etp_stream_t stream);
 int etp_pano_embed_bwd(int dtype, const float* dy, const void* a, const void* d, const float* loc, const int64_t* nav,
                        const float* stats, const float* const* params, float* const* grads, void* da, void* dd, int M, int H,
                        etp_stream_t stream);
 
-/* forward_navigation vilmodel_cmt.py:728-730: x = img + step_emb[step] + LN(pos.Wp^T+bp)  (img, x, dx fp32). */
+/* forward_navigation vilmodel_cmt.py:728-730: x = img + step_emb[step] + LN(pos.Wp^T+bp)  (img, x, dx fp32; x_lp may be NULL).
+ * Backward: d_step_emb (rows named by step_ids only), d_w_pos [H, pos_dim], d_b_pos, dgamma, dbeta are ACCUMULATED (+=). */
 int etp_gmap_embed_fwd(int dtype, const float* img, const int64_t* step_ids, const float* pos, const float* step_emb,
                        const float* w_pos, const float* b_pos, const float* gamma, const float* beta, float* x, void* x_lp,
                        float* stats, int M, int H, int pos_dim, etp_stream_t stream);
@@ -194,7 +200,9 @@ int etp_gmap_embed_bwd(int dtype, const float* dx, const int64_t* step_ids, cons
                        float* d_b_pos, float* dgamma, float* dbeta, int M, int H, int pos_dim, etp_stream_t stream);
 
 /* NextActionPrediction tail vilmodel_cmt.py:651-661 + masked_fill_ :742-744: logits = LN(r).w2 + b2, -inf where
- * visited or !valid; r = relu(x.W1^T+b1) from etp_gemm(ETP_ACT_RELU). */
+ * visited or !valid; r = relu(x.W1^T+b1) from etp_gemm(ETP_ACT_RELU).  visited / valid may each be NULL (no such mask).
+ * Backward: dgamma / dbeta / dw2 / db2 are ACCUMULATED (+=); the row output dz (gradient of the pre-ReLU input) is OVERWRITTEN,
+ * exactly 0 on masked rows (whatever dlogits holds there) and where r == 0. */
 int etp_sap_tail_fwd(int dtype, const void* r, const float* gamma, const float* beta, const float* w2, const float* b2,
                      const uint8_t* visited, const uint8_t* valid, float* logits, float* stats, int M, int H,
                      etp_stream_t stream);

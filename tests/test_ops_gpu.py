@@ -395,13 +395,20 @@ def test_streaming_attention_fwd_bwd(Lq, Lk, mask_mode):
     assert (dkv.float() - kvr.grad).abs().max().item() <= tol(dtype, 3) * max(1.0, kvr.grad.abs().max().item() / 4)
 
 
-@pytest.mark.parametrize("B,Lt", [(5, 24), (32, 80), (2, 130), (1, 7)])
-def test_text_embedding_fwd_bwd(B, Lt):
+@pytest.mark.parametrize("B,Lt,H,eps,dtype", [
+    pytest.param(5, 24, 768, 1e-12, _lib.ETP_F32, id="5-24"), pytest.param(32, 80, 768, 1e-12, _lib.ETP_F32, id="32-80"),
+    pytest.param(2, 130, 768, 1e-12, _lib.ETP_F32, id="2-130"), pytest.param(1, 7, 768, 1e-12, _lib.ETP_F32, id="1-7"),
+    pytest.param(32, 80, 768, 1e-12, _lib.ETP_BF16, id="32-80-bf16"),
+    pytest.param(5, 24, 768, 1e-5, _lib.ETP_BF16, id="5-24-bf16-eps1e-5"),      # the XLM-R LayerNorm of workload c4
+    pytest.param(2, 130, 256, 1e-5, _lib.ETP_BF16, id="2-130-H256-bf16-eps1e-5"),
+    pytest.param(3, 9, 256, 1e-12, _lib.ETP_F32, id="3-9-H256")])
+def test_text_embedding_fwd_bwd(B, Lt, H, eps, dtype):
     """BertEmbeddings (vilmodel_cmt.py:62-77): LN(word[id] + pos[l] + type[0]) and its backward -- the position-embedding
     gradient is a per-position segment sum over the batch, the word-table gradient a scatter-add with repeated ids and the
-    padding row 0 left at zero (:53)."""
+    padding row 0 left at zero (:53).  bf16 mode: the operand copy y_lp is the round-to-nearest-even of y, bit for bit.  The
+    parameter gradients accumulate into what the buffers held (include/etpnav_hip.h)."""
     torch.manual_seed(B * 131 + Lt)
-    H, vocab = 768, 300
+    vocab = 300
     word = torch.randn(vocab, H, device=DEV); pos = torch.randn(Lt + 3, H, device=DEV); typ = torch.randn(2, H, device=DEV)
     gamma = torch.rand(H, device=DEV) + 0.5; beta = torch.randn(H, device=DEV)
     ids = torch.randint(1, vocab, (B, Lt), device=DEV)
@@ -410,23 +417,28 @@ def test_text_embedding_fwd_bwd(B, Lt):
     wr, pr, tr = (t.clone().requires_grad_(True) for t in (word, pos, typ))
     gr, br = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
     emb = torch.nn.functional.embedding(ids, wr, padding_idx=0) + pr[:Lt][None] + tr[0]
-    ref = torch.nn.functional.layer_norm(emb, (H,), gr, br, 1e-12)
-    y = torch.empty(B * Lt, H, device=DEV); stats = torch.empty(B * Lt, 2, device=DEV)
-    check(L().etp_text_embed_fwd(_lib.ETP_F32, ptr(ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(beta), ptr(y), None,
-                                  ptr(stats), B, Lt, H, 1e-12, stream()), "text_embed_fwd")
+    ref = torch.nn.functional.layer_norm(emb, (H,), gr, br, eps)
+    y = torch.full((B * Lt, H), float("nan"), device=DEV); stats = torch.full((B * Lt, 2), float("nan"), device=DEV)
+    y_lp = torch.full((B * Lt, H), float("nan"), device=DEV, dtype=torch.bfloat16) if dtype == _lib.ETP_BF16 else None
+    check(L().etp_text_embed_fwd(dtype, ptr(ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(beta), ptr(y), ptr(y_lp),
+                                  ptr(stats), B, Lt, H, eps, stream()), "text_embed_fwd")
+    torch.cuda.synchronize()
     assert (y.view(B, Lt, H) - ref).abs().max().item() < 2e-5
+    if y_lp is not None:
+        assert torch.equal(y_lp.view(torch.int16), y.to(torch.bfloat16).view(torch.int16)), "y_lp is not the RNE copy of y"
     dy = torch.randn(B * Lt, H, device=DEV)
     ref.backward(dy.view(B, Lt, H))
-    dword = torch.zeros_like(word); dpos = torch.zeros_like(pos); dtyp = torch.zeros(H, device=DEV)
-    dg = torch.zeros(H, device=DEV); db = torch.zeros(H, device=DEV)
-    check(L().etp_text_embed_bwd(_lib.ETP_F32, ptr(dy), ptr(ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(stats),
+    dword0 = torch.randn_like(word); dword0[0] = 0; dpos0 = torch.randn_like(pos); dtyp0 = torch.randn(H, device=DEV)
+    dg0 = torch.randn(H, device=DEV); db0 = torch.randn(H, device=DEV)
+    dword, dpos, dtyp, dg, db = (t.clone() for t in (dword0, dpos0, dtyp0, dg0, db0))
+    check(L().etp_text_embed_bwd(dtype, ptr(dy), ptr(ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(stats),
                                   ptr(dword), ptr(dpos), ptr(dtyp), ptr(dg), ptr(db), B, Lt, H, stream()), "text_embed_bwd")
     torch.cuda.synchronize()
     tol_ = lambda g: 2e-5 * max(1.0, g.abs().max().item())
-    assert (dword - wr.grad).abs().max().item() < tol_(wr.grad) and dword[0].abs().max().item() == 0
-    assert (dpos - pr.grad).abs().max().item() < tol_(pr.grad)
-    assert (dtyp - tr.grad[0]).abs().max().item() < tol_(tr.grad)
-    assert (dg - gr.grad).abs().max().item() < tol_(gr.grad) and (db - br.grad).abs().max().item() < tol_(br.grad)
+    assert (dword - dword0 - wr.grad).abs().max().item() < tol_(wr.grad) and dword[0].abs().max().item() == 0
+    assert (dpos - dpos0 - pr.grad).abs().max().item() < tol_(pr.grad)
+    assert (dtyp - dtyp0 - tr.grad[0]).abs().max().item() < tol_(tr.grad)
+    assert (dg - dg0 - gr.grad).abs().max().item() < tol_(gr.grad) and (db - db0 - br.grad).abs().max().item() < tol_(br.grad)
 
 
 def test_cross_entropy_and_gather():
@@ -558,9 +570,17 @@ def test_gemm_group_forward_products(dtype):
 
 
 @pytest.mark.parametrize("dtype", [_lib.ETP_F32, _lib.ETP_BF16])
-@pytest.mark.parametrize("M", [7, 512, 2560, 5000])
-def test_layer_norm_backward_two_stage(dtype, M):
-    """ln_bwd_s with per-workgroup slabs + ln_part_reduce == autograd of F.layer_norm (dx, dgamma, dbeta accumulate)."""
+@pytest.mark.parametrize("M,cap", [pytest.param(7, None, id="7"), pytest.param(512, None, id="512"), pytest.param(2560, None, id="2560"),
+                                   pytest.param(5000, None, id="5000"), pytest.param(8192, None, id="8192"),
+                                   pytest.param(8192, 2048, id="8192-LNBWD_GRID2048")])
+def test_layer_norm_backward_two_stage(dtype, M, cap, etp_opt):
+    """ln_bwd_s with per-workgroup slabs + ln_part_reduce == autograd of F.layer_norm (dx, dgamma, dbeta accumulate).
+    M = 8192 (the c4 text rows) takes two rounds at the default cap of 1024 workgroups.  The slab buffer is allocated TWICE
+    the size etp_ln_bwd_part_bytes reports, its second half filled with a sentinel that must survive: with LNBWD_GRID = 2048
+    the block cap used to stay unclamped and stage 1 wrote 2048 slabs (exactly 2x the reported size at M = 8192) into a
+    buffer sized for 1024."""
+    if cap is not None:
+        etp_opt("LNBWD_GRID", cap)
     torch.manual_seed(M)
     H = 768
     x = torch.randn(M, H, device=DEV) * 2 + 0.3
@@ -574,11 +594,14 @@ def test_layer_norm_backward_two_stage(dtype, M):
     dx = torch.empty(M, H, device=DEV); dxt = torch.empty(M, H, device=DEV, dtype=tdt(dtype))
     dg0 = torch.randn(H, device=DEV); db0 = torch.randn(H, device=DEV)
     dg, db = dg0.clone(), db0.clone()
-    part = torch.empty(int(L().etp_ln_bwd_part_bytes(M, H)), dtype=torch.uint8, device=DEV)
+    nbytes = int(L().etp_ln_bwd_part_bytes(M, H))
+    part = torch.empty(2 * nbytes, dtype=torch.uint8, device=DEV)
+    part[nbytes:] = 0xA5
     check(L().etp_ln_stream_bwd_stage1(dtype, ptr(dy), ptr(x), ptr(stats), ptr(gmm), ptr(add), ptr(dx), ptr(dxt), ptr(dg), ptr(db),
                                        ptr(part), M, H, stream()), "ln stage1")
     check(L().etp_ln_part_reduce(ptr(part), M, H, ptr(dg), ptr(db), stream()), "ln stage2")
     torch.cuda.synchronize()
+    assert bool((part[nbytes:] == 0xA5).all()), f"stage 1 wrote past the {nbytes} bytes etp_ln_bwd_part_bytes reported"
     assert (dx - (xr.grad + add)).abs().max().item() < 2e-4
     assert (dxt.float() - (xr.grad + add)).abs().max().item() <= tol(dtype, 4)
     assert (dg - dg0 - gr.grad).abs().max().item() < 2e-4 * math.sqrt(M)
