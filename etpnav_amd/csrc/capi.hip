@@ -282,6 +282,10 @@ int etp_attn_fwd(const etp_attn_desc* d, etp_stream_t s) {
   ETP_REQUIRE(d->ldS >= d->Lk && d->ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
   return attn_fwd_impl(d->dtype, d->heads, to_buf(*d), d->P, d->ctx, d->ldc, d->alpha, (hipStream_t)s);
 }
+int etp_attn_family(const etp_attn_desc* d) {
+  ETP_REQUIRE(d && d->Q && d->K && d->V, "null pointer");
+  return attn_family(d->dtype, to_buf(*d), d->ldc);
+}
 int etp_attn_bwd(const etp_attn_bwd_desc* d, etp_stream_t s) {
   ETP_REQUIRE(d && d->f.Q && d->f.K && d->f.V && d->f.P && d->dctx && d->dP && d->dQ && d->dK && d->dV, "null pointer");
   ETP_REQUIRE(d->f.ldS >= d->f.Lk && d->f.ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");

@@ -118,6 +118,9 @@ bool attn_fused_ok(int dt, const AttnBuf& a, long ldc);
 int attn_fused_fwd(int dt, int nh, const AttnBuf& a, void* P, void* ctx, long ldc, float alpha, hipStream_t st, Drop drop);
 int attn_fused_bwd(int dt, int nh, const AttnBuf& a, const void* P, const void* dctx, long ldd, void* dQ, long lddq, void* dK,
                    long lddk, void* dV, long lddv, float alpha, float* d_sp_w, float* d_sp_b, hipStream_t st, Drop drop);
+// the family attn_fwd_impl runs for (dt, a, ldc): the *_ok predicates above tried in its order (planner.hip).  Values = etp_attn_family's.
+enum { ATTN_FAMILY_GEMM = 0, ATTN_FAMILY_TILE = 1, ATTN_FAMILY_ROWS = 2, ATTN_FAMILY_FLASH = 3 };
+int attn_family(int dt, const AttnBuf& a, long ldc);
 // drop = dropout on the attention probabilities (vilmodel_cmt.py:127,346; MHA dropout): inside the fused kernels, or via
 // drop_rows + AttnBuf::Pd on the batched-GEMM path
 int attn_fwd_impl(int dt, int nh, const AttnBuf& a, void* P, void* ctx, long ldc, float alpha, hipStream_t st,

@@ -440,12 +440,22 @@ static int linear_wgrad(const Ctx& c, const void* dY, long ldy, const void* X, l
 static inline const void* offs(const void* p, long elems, size_t es) { return reinterpret_cast<const char*>(p) + elems * es; }
 static inline void* offs(void* p, long elems, size_t es) { return reinterpret_cast<char*>(p) + elems * es; }
 
+// Which kernel family takes a shape: the ONE place the predicates are tried, in this order.  attn_fwd_impl dispatches on it, attn_bwd_impl
+// re-derives the forward's choice from it, and etp_attn_family (capi.hip) reports it to the operator tests, so the three cannot drift.
+int attn_family(int dt, const AttnBuf& a, long ldc) {
+  if (attn_rows_ok(dt, a, ldc)) return ATTN_FAMILY_ROWS;
+  if (attn_fused_ok(dt, a, ldc)) return ATTN_FAMILY_TILE;
+  if (attn_flash_ok(dt, a, ldc)) return ATTN_FAMILY_FLASH;
+  return ATTN_FAMILY_GEMM;
+}
+
 int attn_fwd_impl(int dt, int nh, const AttnBuf& a, void* P, void* ctx, long ldc, float alpha, hipStream_t st, Drop drop) {
   const int dh = 64;
-  if (attn_rows_ok(dt, a, ldc)) return attn_rows_fwd(nh, a, P, ctx, ldc, alpha, st, drop);
+  const int fam = attn_family(dt, a, ldc);
+  if (fam == ATTN_FAMILY_ROWS) return attn_rows_fwd(nh, a, P, ctx, ldc, alpha, st, drop);
   ETP_REQUIRE(a.kv_mod == 0, "per-episode K/V indirection (AttnBuf::kv_mod) needs the register-resident attention kernels (bf16, axes <= 128)");
-  if (attn_fused_ok(dt, a, ldc)) return attn_fused_fwd(dt, nh, a, P, ctx, ldc, alpha, st, drop);
-  if (attn_flash_ok(dt, a, ldc)) return attn_flash_fwd(nh, a, P, ctx, ldc, alpha, st, drop);
+  if (fam == ATTN_FAMILY_TILE) return attn_fused_fwd(dt, nh, a, P, ctx, ldc, alpha, st, drop);
+  if (fam == ATTN_FAMILY_FLASH) return attn_flash_fwd(nh, a, P, ctx, ldc, alpha, st, drop);
   ETP_REQUIRE(drop.p == 0.f || a.Pd, "attention dropout on the unfused path needs the second probability buffer (AttnBuf::Pd)");
   GemmArgs g = base_args();
   // S = alpha * Q K^T
@@ -482,17 +492,18 @@ int attn_bwd_impl(int dt, int nh, const AttnBuf& a, const void* P, const void* d
     // predicate with the forward's ctx leading dimension (= ldo of the saved output when the caller passes it, else ldd).
     const long ldc_f = a.O != nullptr ? a.ldo : ldd;
     const bool dal = lddq % epc == 0 && lddk % epc == 0 && lddv % epc == 0;
-    if (attn_rows_ok(dt, a, ldc_f)) {
+    const int fam = attn_family(dt, a, ldc_f);
+    if (fam == ATTN_FAMILY_ROWS) {
       ETP_REQUIRE(ldd % 8 == 0 && dal, "the forward of this shape kept lse only (register-resident kernels): the backward needs "
                                        "16-byte-aligned dctx / dQ / dK / dV rows");
       return attn_rows_bwd(nh, a, P, dctx, ldd, dQ, lddq, dK, lddk, dV, lddv, alpha, d_sp_w, d_sp_b, st, drop);
     }
     ETP_REQUIRE(a.kv_mod == 0, "per-episode K/V indirection (AttnBuf::kv_mod) needs the register-resident attention kernels (bf16, axes <= 128)");
-    if (attn_fused_ok(dt, a, ldc_f)) {
+    if (fam == ATTN_FAMILY_TILE) {
       if (attn_fused_ok(dt, a, ldd) && dal)
         return attn_fused_bwd(dt, nh, a, P, dctx, ldd, dQ, lddq, dK, lddk, dV, lddv, alpha, d_sp_w, d_sp_b, st, drop);
       // (the LDS-tile forward saved probabilities: the batched-GEMM backward below can read them)
-    } else if (attn_flash_ok(dt, a, ldc_f)) {
+    } else if (fam == ATTN_FAMILY_FLASH) {
       ETP_REQUIRE(a.O != nullptr && a.ldo % epc == 0 && ldd % epc == 0 && dal,
                   "the forward of this shape kept lse only (streaming kernels): the backward needs the forward output (ctx) and "
                   "16-byte-aligned dctx / dQ / dK / dV rows");

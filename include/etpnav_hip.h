@@ -108,7 +108,26 @@ int etp_softmax_bwd(int dtype, const void* P, void* dP, const float* dist, float
  * (BertSelfAttention / BertOutAttention / nn.MultiheadAttention).  P [B,heads,Lq,ldS] is the buffer the forward leaves for the
  * backward of the SAME shape/dtype: probabilities on the tile / batched-GEMM paths (fp32; bf16 with dist on an axis > 128),
  * and for bf16 otherwise only lse = rowmax + log(rowsum) (fp32, [B,heads,Lq] in the front of the buffer) -- the register-resident
- * (both axes <= 128) and streaming kernels recompute the probabilities in backward.  Callers must treat it as opaque. */
+ * (both axes <= 128) and streaming kernels recompute the probabilities in backward.  Callers must treat it as opaque.
+ *
+ * Contract (tests/test_attn_kernels_gpu.py holds every family to it against float64):
+ *   - ctx, dQ, dK, dV are OVERWRITTEN; d_sp_w / d_sp_b ACCUMULATE (one atomicAdd per workgroup: their last bits depend on the order).
+ *   - keymask NULL = every key valid.  mask_mode 0 adds -10000 to an invalid key's score, so a row whose keys are all invalid is the
+ *     softmax of its unmasked scores.  Under mask_mode 1 a query row with NO valid key is OUTSIDE the contract: the register-resident,
+ *     LDS-tile and batched-GEMM kernels return NaN there (exp(-inf - -inf): csrc/attn_rows.hip rows_fwd_kernel, `inv = 1.0f / sum`;
+ *     csrc/norm.hip softmax_fwd_kernel), the streaming kernels 0 (csrc/attn.hip flash_fwd_kernel, `inv = l_run > 0 ? 1 / l_run : 0`).
+ *     The model never forms such a row (every panorama has a view, every instruction a [CLS]).
+ *   - Which kernel family runs (etp_attn_family; tried in this order):
+ *       2 register-resident  bf16, Lq and Lk <= 128; Q / K / V 16-byte aligned, ldq / ldk / ldv / ldc multiples of 8, ldS >= 2;
+ *                            sp_w and sp_b given whenever dist is (switch ATTN_ROWS)
+ *       1 LDS-tile           Lq and Lk <= 128 (fp32: <= 64); Q / K / V 16-byte aligned; ldq / ldk / ldv / ldc / ldS multiples of
+ *                            8 (bf16) or 4 (fp32) (switch ATTN_FUSED; ATTN_Q96 picks the 96 x 96 tile for 64 < Lq, Lk <= 96)
+ *       3 streaming          bf16, Lq or Lk > 128, dist NULL; same alignment as 2, ldS >= 4 (switches ATTN_FLASH and ATTN_FUSED)
+ *       0 batched-GEMM       everything else: fp32 beyond 64, bf16 with dist beyond 128, an operand or leading dimension that is
+ *                            not aligned as above, a switch turned off.  Stores alpha*Q.K^T and dP in the operand dtype.
+ *   - The backward re-derives the forward's family from the same descriptor (it decides what P holds), so the switches, the operand
+ *     alignments and ctx / ldc must be the same for a forward and its backward; families 2 and 3 then also need 16-byte-aligned
+ *     dctx / dQ / dK / dV rows and fail with ETP_ERR_INVALID otherwise. */
 typedef struct etp_attn_desc {
   int32_t dtype, B, heads, Lq, Lk, ldS;
   const void* Q; int64_t ldq;   /* Q rows [B*Lq], head h at column h*64 */
@@ -123,6 +142,9 @@ typedef struct etp_attn_desc {
   float alpha;
 } etp_attn_desc;
 int etp_attn_fwd(const etp_attn_desc* d, etp_stream_t stream);
+/* Host only, launches nothing: the family etp_attn_fwd would run for `d` under the current switches -- 0 batched-GEMM, 1 LDS-tile,
+ * 2 register-resident, 3 streaming (the same predicates in the same order, from the helper the dispatch itself uses); < 0 on error. */
+int etp_attn_family(const etp_attn_desc* d);
 /* Self-attention forward with the QKV PROJECTION folded in (round 6): Q / K / V of `d` (Lq == Lk, rows of one token block, e.g. the
  * three column blocks of a [B*L, 3*heads*64] stash) are OUTPUTS -- each (batch, head) workgroup computes
  *   [Q | K | V][b, l, h*64 : h*64+64] = x[b*L + l, :] . w_qkv[sec*heads*64 + h*64 + (0..63), :]^T + b_qkv     (sec = 0, 1, 2)
