@@ -83,14 +83,16 @@ unsigned row_launch_lds(const void* kern, int family, unsigned smem) {
 }
 
 // ---- run-time switches (options.h) -------------------------------------------------------------------------------------------
-static const char* const kOptNames[OPT_COUNT] = {
+// positional: entry i names enum value i of options.h (the length is checked below, the order is not)
+static const char* const kOptNames[] = {
     "MM32", "MM32_GROUP", "MM32_K2", "GEMM_TILE", "GROUP_TILE", "GEMM_WIDE", "GEMM_SMALL", "GEMM_XCD", "ATTN_FUSED", "ATTN_FLASH", "ATTN_Q96",
-    "ATTN_ROWS", "LNBWD_GRID", "LNBWD_TWO_STAGE", "WGRAD_GROUP", "FLUSH_DELAY", "FLUSH_EVERY", "ROW_EXCLUSIVE",
-    "ATTN_PROJ", "NAV_TAIL", "TXT_LAST_SPLIT", "TXT_TAIL", "ATTN_QKV",
+    "ATTN_ROWS", "LNBWD_GRID", "LNBWD_TWO_STAGE", "WGRAD_GROUP", "FLUSH_DELAY", "ROW_EXCLUSIVE",
+    "ATTN_PROJ", "NAV_TAIL", "TXT_LAST_SPLIT", "ATTN_QKV",
 #ifdef ETP_EXPERIMENTS
     "SKIP_LN", "SKIP_ATTN", "SKIP_WGRAD",
 #endif
 };
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) == OPT_COUNT, "kOptNames must name every switch of enum Opt (options.h), in its order");
 // two value slots per switch: a setter writes the slot that is NOT published and then flips the index, so a concurrent reader never
 // sees a half-written string (readers hold no lock; setters are serialised)
 static char g_opt_val[OPT_COUNT][2][32];

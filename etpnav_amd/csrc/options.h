@@ -3,6 +3,10 @@
 // three of them on every GEMM launch.  A lookup is an array read.
 // Switches whose results are WRONG by design (timing-only drop-one builds: SKIP_LN / SKIP_ATTN / SKIP_WGRAD) are not in the shipped
 // library any more: they exist only under -DETP_EXPERIMENTS.
+// Removed, because they lost on every workload measured and only a user-set variable reached them: TXT_TAIL (text-embedding backward on
+// the aux2 stream: -0.26 % alone, 3.991 against 3.977 ms once NAV_TAIL is on), FLUSH_EVERY (round-3 measurement knob, never off 1) and
+// the third FLUSH_DELAY mode (2: 4.14 against 4.10 ms).  FLUSH_DELAY is a 0 / 1 switch now: any other value, the former 2 included,
+// behaves as 1.  The enum below and kOptNames (capi.hip) are positional and must stay in the same order.
 #pragma once
 
 namespace etp {
@@ -18,12 +22,12 @@ enum Opt {
   OPT_GEMM_XCD,         // 0: XCD-chunked tile order off
   OPT_ATTN_FUSED, OPT_ATTN_FLASH, OPT_ATTN_Q96, OPT_ATTN_ROWS,
   OPT_LNBWD_GRID, OPT_LNBWD_TWO_STAGE,
-  OPT_WGRAD_GROUP, OPT_FLUSH_DELAY, OPT_FLUSH_EVERY,
+  OPT_WGRAD_GROUP,
+  OPT_FLUSH_DELAY,      // text backward: 0 = a layer's weight gradients forked at its end, anything else (1, and the former 2) = behind the next layer's FFN-down dgrad; unset = by grid
   OPT_ROW_EXCLUSIVE,    // 0: the row kernels of DESIGN.md §3.6 launch WITHOUT the CU-exclusive LDS request (neighbour-matrix test only)
   OPT_ATTN_PROJ,        // out-projection dgrad folded into the register-resident attention backward: unset = when batch*heads <= CUs, 0 never, 1 always
   OPT_NAV_TAIL,         // bit 0: the node-embedding backward as a leaf on the weight-gradient stream; bit 1: d txt_embeds joined by its consumers (default 3)
   OPT_TXT_LAST_SPLIT,   // text layer 0's attention weight gradients forked each as soon as it can: unset = for multi-round grids (config 4), 0 never, 1 always
-  OPT_TXT_TAIL,         // 1: the text-embedding backward on the aux2 stream beside the weight-gradient backlog (measured neutral: default off)
   OPT_ATTN_QKV,         // QKV projection folded into the register-resident self-attention forward: unset / 0 never (measured slower), 1 always
 #ifdef ETP_EXPERIMENTS
   OPT_SKIP_LN, OPT_SKIP_ATTN, OPT_SKIP_WGRAD,

@@ -280,10 +280,21 @@ struct Ctx {
   // a layer's four to seven small TN products fill the chip together, which none of them does alone.
   std::vector<GemmArgs>* wq;
 };
+// The two queues of ONE backward entry point, hooked into its Ctx.  Ctx holds pointers only: its by-value copies (a Ctx with another
+// `st`) keep sharing this one pair.
+struct SideQueues {
+  std::vector<std::function<int()>> pend;
+  std::vector<GemmArgs> wq;
+  explicit SideQueues(Ctx& c) {
+    if (c.sw != c.st) c.pend = &pend;
+    c.wq = &wq;
+  }
+  SideQueues(const SideQueues&) = delete;
+};
 // dropout sites: (entry point, layer, slot) -> independent mask streams
 enum { SITE_EMBED = 0, SITE_ATT_P = 1, SITE_ATT_O = 2, SITE_FFN_O = 3, SITE_FFN_I = 4, SITE_X_P = 5, SITE_X_O = 6, SITE_HEAD = 7,
        SITE_ENV = 8 };
-enum { MODE_TXT = 1, MODE_PANO = 2, MODE_NAV = 3 };
+enum { MODE_TXT = 1, MODE_PANO = 2, MODE_NAV = 3, MODE_MLM = 4 };   // the values seed the dropout streams: never renumber
 static inline Drop site(const Ctx& c, float p, int mode, int layer, int slot) {
   return p > 0.f ? drop_site(p, c.pl->drop_seed, (uint32_t)(mode << 16 | layer << 4 | slot)) : drop_none();
 }
@@ -672,13 +683,20 @@ static int ln_bwd_chain(const Ctx& c, const float* dy, const float* x, const flo
   return on_side(c, [=]() -> int { return ln_part_reduce(part, M, H, dg, db, sw); });
 }
 
+// self attention on a packed [Bn*L, 3H] Q|K|V buffer (the backward adds O / ldo)
+static AttnBuf qkv_buf(const Ctx& c, void* qkv, void* Pd, int Bn, int L, const uint8_t* keymask, int mask_mode, const float* dist,
+                       const float* sp_w, const float* sp_b) {
+  const long ld = 3L * c.H;
+  AttnBuf a{qkv, ld, offs(qkv, c.H, c.es), ld, offs(qkv, 2 * c.H, c.es), ld, Bn, L, L, (int)round_up(L, 8), keymask, mask_mode, dist, sp_w,
+            sp_b};
+  a.Pd = Pd;
+  return a;
+}
 // y = LN(dropout(dense(attn(x))) + x)
 static int self_att_fwd(const Ctx& c, const AttnP& p, const Act& x, SelfAttStash& s, int Bn, int L, const uint8_t* keymask,
                         const float* dist, const float* sp_w, const float* sp_b, float eps, int mode, int layer) {
   const int H = c.H, M = Bn * L;
-  AttnBuf a{s.qkv, 3L * H, offs(s.qkv, H, c.es), 3L * H, offs(s.qkv, 2 * H, c.es), 3L * H, Bn, L, L, (int)round_up(L, 8),
-            keymask, 0, dist, sp_w, sp_b};
-  a.Pd = s.Pd;
+  AttnBuf a = qkv_buf(c, s.qkv, s.Pd, Bn, L, keymask, 0, dist, sp_w, sp_b);
   ETP_TRY(attn_fwd_qkv(c, a, s.P, s.ctx, x.t, p.qkv_w, p.qkv_b, s.qkv, M, att(c, mode, layer, SITE_ATT_P)));
   ETP_TRY(linear_fwd_s(c, s.ctx, H, p.o_w, p.o_b, s.s, M, H, H, x.f, hid(c, mode, layer, SITE_ATT_O)));
   return ln_fwd_s(c.dt, s.s, c.pl->pf(p.ln_g), c.pl->pf(p.ln_b), s.y.f, lp(s.y, c.dt), s.st, M, H, eps, c.st);
@@ -691,15 +709,12 @@ static int self_att_bwd(const Ctx& c, const AttnP& p, const Act& x, const SelfAt
                         const uint8_t* keymask, const float* dist, const float* sp_w, const float* sp_b, float* d_sp_w,
                         float* d_sp_b, float* g, const BwdWs& w, int mode, int layer, bool tail_flush = false) {
   const int H = c.H, M = Bn * L;
-  etp_planner* pl = c.pl;
   const Drop dh = hid(c, mode, layer, SITE_ATT_O);
   ETP_TRY(ln_bwd_chain(c, g, s.s, s.st, p.ln_g, p.ln_b, nullptr, w.t1.f, lp2(c, w.t1, dh), M, dh, w.lnp));   // t1.f = ds, operand copy = ds * mask
   const void* ds = op2(c, w.t1, dh);
   ETP_TRY(linear_wgrad(c, ds, H, s.ctx, H, p.o_w, p.o_b, M, H, H));
   if (tail_flush) ETP_TRY(flush_side(c));
-  AttnBuf a{s.qkv, 3L * H, offs(s.qkv, H, c.es), 3L * H, offs(s.qkv, 2 * H, c.es), 3L * H, Bn, L, L, (int)round_up(L, 8),
-            keymask, 0, dist, sp_w, sp_b};
-  a.Pd = s.Pd;
+  AttnBuf a = qkv_buf(c, s.qkv, s.Pd, Bn, L, keymask, 0, dist, sp_w, sp_b);
   a.O = s.ctx; a.ldo = H;
   ETP_TRY(attn_bwd_proj(c, a, s.P, ds, p.o_w, w.t2, M, w.dP, w.dqkv, 3L * H, offs(w.dqkv, H, c.es), 3L * H,                    // t2 = dctx
                         offs(w.dqkv, 2 * H, c.es), 3L * H, d_sp_w, d_sp_b, att(c, mode, layer, SITE_ATT_P)));
@@ -715,9 +730,8 @@ static int ffn_fwd(const Ctx& c, const FfnP& p, const Act& x, FfnStash& f, int M
   return ln_fwd_s(c.dt, f.s, c.pl->pf(p.ln_g), c.pl->pf(p.ln_b), f.y.f, lp(f.y, c.dt), f.st, M, H, eps, c.st);
 }
 static int ffn_bwd(const Ctx& c, const FfnP& p, const Act& x, const FfnStash& f, int M, float* g, const BwdWs& w, int mode,
-                   int layer, const float* g_in = nullptr, int flush_behind = 0) {
+                   int layer, const float* g_in = nullptr, bool flush_behind = false) {
   const int H = c.H, I = c.I;
-  etp_planner* pl = c.pl;
   const Drop dh = hid(c, mode, layer, SITE_FFN_O);
   ETP_TRY(ln_bwd_chain(c, g_in ? g_in : g, f.s, f.st, p.ln_g, p.ln_b, nullptr, w.t1.f, lp2(c, w.t1, dh), M, dh, w.lnp));
   const void* ds = op2(c, w.t1, dh);
@@ -725,11 +739,70 @@ static int ffn_bwd(const Ctx& c, const FfnP& p, const Act& x, const FfnStash& f,
   ETP_TRY(linear_dgrad(c, ds, H, p.o_w, w.dI, I, M, H, I, ETP_ACT_MUL_Z, f.z, I, nullptr, 0));               // dI = dz
   // the PREVIOUS layer's weight gradients (held back at the end of that layer) + this layer's FFN-down one start behind this launch:
   // the 480-workgroup, two-per-CU dgrad above then finds the chip free instead of queueing behind 432 resident leaf workgroups
-  if (flush_behind == 1) ETP_TRY(flush_side(c));
+  // (behind the whole FFN half instead, so that this layer's FFN pair rides along: 4.14 against 4.10 ms here and 4.18 at the layer's end)
+  if (flush_behind) ETP_TRY(flush_side(c));
   ETP_TRY(linear_wgrad(c, w.dI, I, x.t, H, p.i_w, p.i_b, M, I, H));
-  ETP_TRY(linear_dgrad_s(c, w.dI, I, p.i_w, g, M, I, H, w.t1.f));                                             // g = dx
-  if (flush_behind == 2) ETP_TRY(flush_side(c));      // variant: behind the whole FFN half (this layer's FFN pair rides along)
-  return ETP_OK;
+  return linear_dgrad_s(c, w.dI, I, p.i_w, g, M, I, H, w.t1.f);                                               // g = dx
+}
+
+// ---- cross attention (BertXAttention): queries from one side, keys / values from the other --------------------------
+// Lq / Lk: query and key axis (navigation: nodes / text, forward_lang2visn: text / nodes)
+static CrossStash plan_cross(Bump& b, int dt, int Bn, int nh, int Lq, int Lk, int H) {
+  const size_t es = dtype_size(dt);
+  const long Mq = (long)Bn * Lq, Mk = (long)Bn * Lk;
+  const size_t pbytes = (size_t)Bn * nh * Lq * round_up(Lk, 8) * es;
+  CrossStash s;
+  s.q = b.take(Mq * H * es);
+  s.kv = b.take(Mk * 2 * H * es);
+  s.P = b.take(pbytes);
+  s.ctx = b.take(Mq * H * es);
+  s.s = (float*)b.take(Mq * H * 4);
+  s.st = (float*)b.take(Mq * 2 * sizeof(float));
+  s.y = take_act(b, dt, Mq * H);
+  s.Pd = attn_needs_unfused(dt, Lq, Lk) ? b.take(pbytes) : nullptr;
+  return s;
+}
+struct CrossWs { BwdWs w; void *dq, *dkv, *dPx; };     // (w.dqkv and w.dP stay unused here: the block has dq / dkv / dPx of its own shapes)
+static CrossWs plan_cross_ws(Bump& b, int dt, int Bn, int nh, int Lq, int Lk, int H, int I) {
+  const size_t es = dtype_size(dt);
+  CrossWs x;
+  x.w = plan_ws(b, dt, (long)Bn * Lq, Bn, nh, Lq, (int)round_up(Lq, 8), H, I);
+  x.dq = b.take((long)Bn * Lq * H * es);
+  x.dkv = b.take((long)Bn * Lk * 2 * H * es);
+  x.dPx = b.take((size_t)Bn * nh * Lq * round_up(Lk, 8) * es);
+  return x;
+}
+struct CrossDims { int Bn, Lq, Lk; const uint8_t* keymask; int kv_mod; };
+static AttnBuf cross_buf(const Ctx& c, const CrossStash& s, void* kv, const CrossDims& d) {
+  const int H = c.H;
+  AttnBuf a{s.q, (long)H, kv, 2L * H, offs(kv, H, c.es), 2L * H, d.Bn, d.Lq, d.Lk, (int)round_up(d.Lk, 8), d.keymask, 0, nullptr, nullptr,
+            nullptr};
+  a.Pd = s.Pd;
+  a.kv_mod = d.kv_mod;
+  return a;
+}
+// y = LN(dropout(dense(attn(q, kv))) + x); q and the K|V block `kv` are projected by the caller
+static int cross_att_fwd(const Ctx& c, const XLayerP& p, const Act& x, CrossStash& s, void* kv, const CrossDims& d, float eps, int mode,
+                         int layer) {
+  const int H = c.H, M = d.Bn * d.Lq;
+  ETP_TRY(attn_fwd_impl(c.dt, c.nh, cross_buf(c, s, kv, d), s.P, s.ctx, H, 0.125f, c.st, att(c, mode, layer, SITE_X_P)));
+  ETP_TRY(linear_fwd_s(c, s.ctx, H, p.xo_w, p.xo_b, s.s, M, H, H, x.f, hid(c, mode, layer, SITE_X_O)));
+  return ln_fwd_s(c.dt, s.s, c.pl->pf(p.xln_g), c.pl->pf(p.xln_b), s.y.f, lp(s.y, c.dt), s.st, M, H, eps, c.st);
+}
+// g (fp32) = dL/dy in; dL/dx goes to dx (may be g); dK|dV of the block go to dkv [Bn*Lk, 2H] (the caller projects them back)
+static int cross_att_bwd(const Ctx& c, const XLayerP& p, const Act& x, const CrossStash& s, void* kv, const CrossDims& d, const float* g,
+                         float* dx, void* dkv, const CrossWs& w, int mode, int layer) {
+  const int H = c.H, M = d.Bn * d.Lq;
+  const Drop dh = hid(c, mode, layer, SITE_X_O);
+  ETP_TRY(ln_bwd_chain(c, g, s.s, s.st, p.xln_g, p.xln_b, nullptr, w.w.t1.f, lp2(c, w.w.t1, dh), M, dh, w.w.lnp));
+  const void* ds = op2(c, w.w.t1, dh);
+  ETP_TRY(linear_wgrad(c, ds, H, s.ctx, H, p.xo_w, p.xo_b, M, H, H));
+  AttnBuf a = cross_buf(c, s, kv, d);
+  a.O = s.ctx; a.ldo = H;
+  ETP_TRY(attn_bwd_proj(c, a, s.P, ds, p.xo_w, w.w.t2, M, w.dPx, w.dq, H, dkv, 2L * H, offs(dkv, H, c.es), 2L * H, nullptr, nullptr,
+                        att(c, mode, layer, SITE_X_P)));
+  ETP_TRY(linear_wgrad(c, w.dq, H, x.t, H, p.q_w, p.q_b, M, H, H));
+  return linear_dgrad_s(c, w.dq, H, p.q_w, dx, M, H, H, w.w.t1.f);
 }
 
 // ======================================================================================
@@ -750,6 +823,19 @@ static TxtStash plan_txt(const etp_planner* pl, Bump& b, int Bn, int L) {
     t.ffn.push_back(plan_ffn(b, dt, M, H, pl->cfg.inter));
   }
   return t;
+}
+// Backward scratch of forward_txt: the running gradient, then a fresh set per sub-block in the order the backward visits them.  Every
+// layer-range call carves the WHOLE buffer, so consecutive ranges continue in the same g and never share a set.
+struct TxtWs { float* g; std::vector<BwdWs> ffn, att; };
+static TxtWs plan_txt_ws(const etp_planner* pl, Bump& b, int Bn, int L) {
+  const etp_config& c = pl->cfg;
+  const long M = (long)Bn * L;
+  TxtWs w{(float*)b.take((size_t)M * c.hidden * 4), std::vector<BwdWs>(c.n_l), std::vector<BwdWs>(c.n_l)};
+  for (int l = c.n_l - 1; l >= 0; --l) {
+    w.ffn[l] = plan_ws(b, c.dtype, M, Bn, c.heads, L, (int)round_up(L, 8), c.hidden, c.inter);
+    w.att[l] = plan_ws(b, c.dtype, M, Bn, c.heads, L, (int)round_up(L, 8), c.hidden, c.inter);
+  }
+  return w;
 }
 
 }  // namespace etp
@@ -882,9 +968,7 @@ int64_t etp_txt_stash_bytes(const etp_planner* p, int B, int L) {
 int64_t etp_txt_ws_bytes(const etp_planner* p, int B, int L) {
   if (!p) return 0;
   Bump b(nullptr);
-  b.take((size_t)B * L * p->cfg.hidden * 4);
-  for (int l = 0; l < 2 * p->cfg.n_l; ++l)
-    plan_ws(b, p->cfg.dtype, (long)B * L, B, p->cfg.heads, L, (int)round_up(L, 8), p->cfg.hidden, p->cfg.inter);
+  plan_txt_ws(p, b, B, L);
   return (int64_t)b.off + 256;
 }
 
@@ -928,20 +1012,16 @@ int etp_txt_bwd_range(etp_planner* p, const float* dout, const int64_t* ids, con
   // the one event is re-recorded by every deferral and aux2 is in-order, so the latest record covers the earlier ones), and a stream that
   // never deferred never waits -- a stale event must not be waited for inside a stream capture
   if (p->dtxt_owed(c.st)) ETP_CHECK_HIP(stream_wait_event(c.st, p->dtxt_ready));
-  std::vector<std::function<int()>> pend;
-  std::vector<GemmArgs> wq;
-  if (c.sw != c.st) c.pend = &pend;
-  c.wq = &wq;
+  SideQueues sq(c);
   Bump b(stash);
   TxtStash t = plan_txt(p, b, B, L);
   Bump wb(ws);
+  const TxtWs w = plan_txt_ws(p, wb, B, L);
   const int H = c.H, M = B * L;
-  float* g = (float*)wb.take((size_t)M * H * 4);
+  float* g = w.g;
   if (layer_hi == p->cfg.n_l && p->cfg.n_l == 0) ETP_TRY(copy_f32(dout, g, (long)M * H, c.st));
   for (int l = p->cfg.n_l - 1; l >= 0; --l) {
     const Act x = l == 0 ? t.x0 : t.ffn[l - 1].y;
-    BwdWs wf = plan_ws(wb, c.dt, M, B, c.nh, L, (int)round_up(L, 8), H, c.I);   // same carving in every call
-    BwdWs wa = plan_ws(wb, c.dt, M, B, c.nh, L, (int)round_up(L, 8), H, c.I);
     if (l >= layer_hi || l < layer_lo) continue;
     stamp_mark(c.st, 2200 + 10 * l);
     // the top layer reads the incoming gradient in place (dout) and leaves dL/dx in the running buffer g
@@ -950,12 +1030,12 @@ int etp_txt_bwd_range(etp_planner* p, const float* dout, const int64_t* ids, con
     // step against 27.9 us alone (profiles/r05_chain_vs_isolated.txt), 9 x 37 us.  They are held back and go out right BEHIND that dgrad
     // (1, the default): the leaf work then shares the chip with the FFN-up dgrad, LayerNorm, out-projection and attention backward, whose
     // one-per-CU 74-KB workgroups and small kernels leave room beside it.  Same-box A/B (profiles/r05_ab_runs.json): 4.12 / 4.13 ->
-    // 4.06 / 4.06 ms; behind the whole FFN half (2): 4.14 against 4.10 (1) and 4.18 (0) on a second box.  Only where that dgrad IS one
-    // resident round (at most 512 tiles of 128 x 128: configs 2 and 5): at config 4's 8192 rows it is three rounds anyway and holding
-    // the leaf work back costs 1.4 % (10.77 against 10.62 ms).  ETP_FLUSH_DELAY=0 / 1 / 2 forces a mode.
+    // 4.06 / 4.06 ms; a third mode, behind the whole FFN half, lost to both on a second box (4.14 against 4.10 and 4.18) and is gone.
+    // Only where that dgrad IS one resident round (at most 512 tiles of 128 x 128: configs 2 and 5): at config 4's 8192 rows it is three
+    // rounds anyway and holding the leaf work back costs 1.4 % (10.77 against 10.62 ms).  ETP_FLUSH_DELAY=0 / 1 forces a mode.
     const int delay_env = opt_int(OPT_FLUSH_DELAY, -1);
-    const int delay = delay_env >= 0 ? delay_env : (((long)(M / 128) * (c.I / 128) <= 512) ? 1 : 0);
-    ETP_TRY(ffn_bwd(c, p->txt[l].ffn, t.att[l].y, t.ffn[l], M, g, wf, MODE_TXT, l, l == p->cfg.n_l - 1 ? dout : nullptr, delay));
+    const bool delay = delay_env >= 0 ? delay_env != 0 : (long)(M / 128) * (c.I / 128) <= 512;
+    ETP_TRY(ffn_bwd(c, p->txt[l].ffn, t.att[l].y, t.ffn[l], M, g, w.ffn[l], MODE_TXT, l, l == p->cfg.n_l - 1 ? dout : nullptr, delay));
     stamp_mark(c.st, 2200 + 10 * l + 1);
     // the LAST layer of the backward: its two FFN weight gradients go out now instead of with the attention ones at the end of
     // the layer -- nothing runs behind this layer that could hide them (the step's end waits for the weight-gradient stream)
@@ -969,31 +1049,21 @@ int etp_txt_bwd_range(etp_planner* p, const float* dout, const int64_t* ids, con
     // config 5 +0.5 %; config 4 (8192 rows: long products, the tail is theirs) 10.516 against 10.574 ms, -0.55 %.  Rule: where the
     // weight gradients are NOT held back behind the next layer's dgrad either (delay == 0: multi-round grids); 0 / 1 force it.
     const int split_env = opt_int(OPT_TXT_LAST_SPLIT, -1);
-    const bool last_split = l == 0 && layer_lo == 0 && (split_env >= 0 ? split_env != 0 : delay == 0);
-    ETP_TRY(self_att_bwd(c, p->txt[l].att, x, t.att[l], B, L, mask, nullptr, nullptr, nullptr, nullptr, nullptr, g, wa, MODE_TXT, l,
+    const bool last_split = l == 0 && layer_lo == 0 && (split_env >= 0 ? split_env != 0 : !delay);
+    ETP_TRY(self_att_bwd(c, p->txt[l].att, x, t.att[l], B, L, mask, nullptr, nullptr, nullptr, nullptr, nullptr, g, w.att[l], MODE_TXT, l,
                          last_split));
-    // one fork per layer: this layer's four weight gradients as one grouped launch.  ETP_FLUSH_EVERY=n (measurement knob,
-    // tools/r03_call15.sh) forks every n layers instead: 4n products per launch, fewer launch tails, later start of the leaf work
-    const int every = std::max(1, opt_int(OPT_FLUSH_EVERY, 1));
+    // one fork per layer: this layer's four weight gradients as one grouped launch.  (A fork every n layers -- 4n products per launch,
+    // fewer launch tails, later start of the leaf work -- was a round-3 measurement knob that never left n = 1.)
     if (delay && l != layer_lo) continue;             // held back: goes out behind the next layer's FFN dgrad
-    if (every == 1 || (layer_hi - 1 - l) % every == every - 1 || l == layer_lo) ETP_TRY(flush_side(c));
+    ETP_TRY(flush_side(c));
   }
   if (layer_lo == 0) {
-    // TXT_TAIL=1 (round 6 experiment, default OFF): the embedding backward produces parameter gradients only -- a LEAF, and the last kernel
-    // of the step's chain, which then still waits ~66 us for the weight-gradient backlog (profiles/r06_chain_waits.txt).  On a third stream
-    // (aux2: idle by now) it runs BESIDE that backlog instead of in front of the wait.  Measured (r06_ab_runs.json r6c10): the chain ends
-    // 35 us earlier and the backlog it now shares the chip with takes 28 us longer: -0.26 % alone, and WORSE than without it once the
-    // navigation tail (NAV_TAIL) is off the chain (3.991 against 3.977 ms).  Kept as a switch.
-    hipStream_t se = (opt_on(OPT_TXT_TAIL, false) && c.s3 != c.st && c.s3 != c.sw) ? c.s3 : c.st;
-    if (se != c.st) ETP_TRY(stream_after(p, c.st, se));
+    // The embedding backward is a leaf too, and the last kernel of the step's chain.  On the aux2 stream, beside the weight-gradient backlog
+    // it otherwise waits ~66 us for, it measured -0.26 % alone and WORSE once the navigation tail (NAV_TAIL) is off the chain (3.991
+    // against 3.977 ms, r06_ab_runs.json r6c10): it stays on the chain.
     ETP_TRY(text_embed_bwd(c.dt, g, ids, p->pf(p->word), p->pf(p->pos), p->pf(p->type), p->pf(p->emb_g), t.st0, p->gf(p->word),
-                           p->gf(p->pos), p->gf(p->type), p->gf(p->emb_g), p->gf(p->emb_b), B, L, H, se,
+                           p->gf(p->pos), p->gf(p->type), p->gf(p->emb_g), p->gf(p->emb_b), B, L, H, c.st,
                            hid(c, MODE_TXT, 0, SITE_EMBED)));
-    if (se != c.st) {
-      stamp_mark(c.st, 2299);
-      ETP_TRY(join_wgrads(c));
-      return stream_after(p, se, c.st);
-    }
   }
   stamp_mark(c.st, 2299);
   // a range that stops above layer 0 is followed by another one: with lazy level 2 its weight gradients keep running on the
@@ -1116,7 +1186,7 @@ int etp_pano_fwd(etp_planner* p, const float* rgb, const float* dep, const float
   Bump b(stash);
   PanoStash s = plan_pano(p, b, B, V);
   const etp_config& cf = p->cfg;
-  const int H = c.H, I = c.I, M = B * V, ldS = (int)round_up(V, 8);
+  const int H = c.H, I = c.I, M = B * V;
   stamp_mark(c.st, 1100);
   ETP_LAUNCH(seq_mask_kernel, dim3((M + 255) / 256), dim3(256), 0, c.st, view_lens, s.mask, out_mask, B, V);
   ETP_CHECK_LAUNCH("seq_mask");
@@ -1138,9 +1208,7 @@ int etp_pano_fwd(etp_planner* p, const float* rgb, const float* dep, const float
     PanoLayerStash& t = s.layers[l];
     ETP_TRY(ln_fwd_s(c.dt, x, p->pf(q.n1_g), p->pf(q.n1_b), c.dt == ETP_BF16 ? nullptr : (float*)t.a,
                      c.dt == ETP_BF16 ? t.a : nullptr, t.st1, M, H, 1e-5f, c.st));
-    AttnBuf a{t.qkv, 3L * H, offs(t.qkv, H, c.es), 3L * H, offs(t.qkv, 2 * H, c.es), 3L * H, B, V, V, ldS, s.mask, 1, nullptr,
-              nullptr, nullptr};
-    a.Pd = t.Pd;
+    AttnBuf a = qkv_buf(c, t.qkv, t.Pd, B, V, s.mask, 1, nullptr, nullptr, nullptr);
     ETP_TRY(attn_fwd_qkv(c, a, t.P, t.ctx, t.a, q.in_w, q.in_b, t.qkv, M, hid(c, MODE_PANO, l, SITE_ATT_P)));   // MHA dropout = hidden rate
     ETP_TRY(linear_fwd_s(c, t.ctx, H, q.out_w, q.out_b, t.x1, M, H, H, x, hid(c, MODE_PANO, l, SITE_ATT_O)));
     ETP_TRY(ln_fwd_s(c.dt, t.x1, p->pf(q.n2_g), p->pf(q.n2_b), c.dt == ETP_BF16 ? nullptr : (float*)t.f,
@@ -1158,10 +1226,7 @@ int etp_pano_bwd(etp_planner* p, const float* dout, const float* rgb, const floa
                  int B, int V, float* d_rgb, void* stash, void* ws, etp_stream_t stream) {
   ETP_REQUIRE(p && p->P && p->G && dout && rgb && loc && nav && stash && ws && B > 0 && V > 0, "bad arguments");
   Ctx c = make_ctx(p, stream);
-  std::vector<std::function<int()>> pend;
-  std::vector<GemmArgs> wq;
-  if (c.sw != c.st) c.pend = &pend;
-  c.wq = &wq;
+  SideQueues sq(c);
   Bump b(stash);
   PanoStash s = plan_pano(p, b, B, V);
   const etp_config& cf = p->cfg;
@@ -1195,9 +1260,7 @@ int etp_pano_bwd(etp_planner* p, const float* dout, const float* rgb, const floa
     // attention: x1 = x + dropout1(Wo attn(LN1(x)))
     const void* t2op = op2(c, w.t2, d1);
     ETP_TRY(linear_wgrad(c, t2op, H, t.ctx, H, q.out_w, q.out_b, M, H, H));
-    AttnBuf a{t.qkv, 3L * H, offs(t.qkv, H, c.es), 3L * H, offs(t.qkv, 2 * H, c.es), 3L * H, B, V, V, ldS, s.mask, 1, nullptr,
-              nullptr, nullptr};
-    a.Pd = t.Pd;
+    AttnBuf a = qkv_buf(c, t.qkv, t.Pd, B, V, s.mask, 1, nullptr, nullptr, nullptr);
     a.O = t.ctx; a.ldo = H;
     ETP_TRY(attn_bwd_proj(c, a, t.P, t2op, q.out_w, w.t1, M, w.dP, w.dqkv, 3L * H, offs(w.dqkv, H, c.es), 3L * H,               // t1 = dctx
                           offs(w.dqkv, 2 * H, c.es), 3L * H, nullptr, nullptr, hid(c, MODE_PANO, l, SITE_ATT_P)));
@@ -1239,21 +1302,14 @@ NavStash plan_nav(const etp_planner* pl, Bump& b, int Bn, int L, int G) {
   const int dt = c.dtype;
   const size_t es = dtype_size(dt);
   const long Mg = (long)Bn * G, Mt = (long)Bn * L;
-  const int H = c.hidden, ldL = (int)round_up(L, 8), ldG = (int)round_up(G, 8);
+  const int H = c.hidden, ldG = (int)round_up(G, 8);
   NavStash s;
   s.txtT = dt == ETP_BF16 ? b.take(Mt * H * es) : nullptr;
   s.x0 = take_act(b, dt, Mg * H);
   s.st0 = (float*)b.take(Mg * 2 * sizeof(float));
   for (int l = 0; l < c.n_x; ++l) {
     XStash x;
-    x.cross.q = b.take(Mg * H * es);
-    x.cross.kv = b.take(Mt * 2 * H * es);
-    x.cross.P = b.take((size_t)Bn * c.heads * G * ldL * es);
-    x.cross.ctx = b.take(Mg * H * es);
-    x.cross.s = (float*)b.take(Mg * H * 4);
-    x.cross.st = (float*)b.take(Mg * 2 * sizeof(float));
-    x.cross.y = take_act(b, dt, Mg * H);
-    x.cross.Pd = attn_needs_unfused(dt, G, L) ? b.take((size_t)Bn * c.heads * G * ldL * es) : nullptr;
+    x.cross = plan_cross(b, dt, Bn, c.heads, G, L, H);
     x.self = plan_self(b, dt, Mg, Bn, c.heads, G, ldG, H);
     x.ffn = plan_ffn(b, dt, Mg, H, c.inter);
     s.layers.push_back(x);
@@ -1262,13 +1318,11 @@ NavStash plan_nav(const etp_planner* pl, Bump& b, int Bn, int L, int G) {
   s.str = (float*)b.take(Mg * 2 * sizeof(float));
   return s;
 }
-struct NavCrossWs { BwdWs w; void *dq, *dkv, *dPx; };
-struct NavWs { float* g; BwdWs head; std::vector<BwdWs> ffn, self; std::vector<NavCrossWs> cross; };
+struct NavWs { float* g; BwdWs head; std::vector<BwdWs> ffn, self; std::vector<CrossWs> cross; };
 NavWs plan_nav_ws(const etp_planner* pl, Bump& b, int Bn, int L, int G) {
   const etp_config& c = pl->cfg;
   const int dt = c.dtype;
-  const size_t es = dtype_size(dt);
-  const long Mg = (long)Bn * G, Mt = (long)Bn * L;
+  const long Mg = (long)Bn * G;
   const int ldG = (int)round_up(G, 8);
   NavWs n;
   n.g = (float*)b.take(Mg * c.hidden * 4);
@@ -1276,12 +1330,7 @@ NavWs plan_nav_ws(const etp_planner* pl, Bump& b, int Bn, int L, int G) {
   for (int l = 0; l < c.n_x; ++l) {   // fresh scratch per sub-block (see plan_ws)
     n.ffn.push_back(plan_ws(b, dt, Mg, Bn, c.heads, G, ldG, c.hidden, c.inter));
     n.self.push_back(plan_ws(b, dt, Mg, Bn, c.heads, G, ldG, c.hidden, c.inter));
-    NavCrossWs x;
-    x.w = plan_ws(b, dt, Mg, Bn, c.heads, G, ldG, c.hidden, c.inter);
-    x.dq = b.take(Mg * c.hidden * es);
-    x.dkv = b.take(Mt * 2 * c.hidden * es);
-    x.dPx = b.take((size_t)Bn * c.heads * G * round_up(L, 8) * es);
-    n.cross.push_back(x);
+    n.cross.push_back(plan_cross_ws(b, dt, Bn, c.heads, G, L, c.hidden, c.inter));
   }
   return n;
 }
@@ -1306,34 +1355,30 @@ namespace {
 // keys/values in each of the 4 x-layers at every rollout step (vilmodel_cmt.py:326-328,387-389; ss_trainer_ETP.py:819-822).
 // Layout of the caller-owned cache: [ text in the operand dtype (bf16 mode only) | K|V of x-layer 0 | ... | x-layer n_x-1 ],
 // each K|V block [B*L, 2H] in the operand dtype -- exactly what the cross-attention kernels consume.
-struct KvCache { void* txtT; std::vector<void*> kv; };
-KvCache plan_kv(const etp_planner* pl, void* buf, int Bn, int L) {
+struct KvCache { void* txtT; size_t kv_off; std::vector<void*> kv; };     // kv_off: byte offset of the first K|V block
+KvCache plan_kv(const etp_planner* pl, Bump& b, int Bn, int L) {
   const etp_config& c = pl->cfg;
   const size_t es = dtype_size(c.dtype);
   const long Mt = (long)Bn * L;
-  Bump b(buf);
   KvCache k;
   k.txtT = c.dtype == ETP_BF16 ? b.take(Mt * c.hidden * es) : nullptr;
+  k.kv_off = b.off;
   for (int l = 0; l < c.n_x; ++l) k.kv.push_back(b.take(Mt * 2 * c.hidden * es));
   return k;
-}
-int64_t kv_bytes(const etp_planner* pl, int Bn, int L) {
-  const etp_config& c = pl->cfg;
-  const size_t es = dtype_size(c.dtype);
-  const long Mt = (long)Bn * L;
-  Bump b(nullptr);
-  if (c.dtype == ETP_BF16) b.take(Mt * c.hidden * es);
-  for (int l = 0; l < c.n_x; ++l) b.take(Mt * 2 * c.hidden * es);
-  return (int64_t)b.off + 256;
 }
 }  // namespace
 extern "C" {
 
-int64_t etp_nav_kv_bytes(const etp_planner* p, int B, int L) { return p ? kv_bytes(p, B, L) : 0; }
-int64_t etp_nav_kv_offset(const etp_planner* p, int B, int L) {   // byte offset of the first K|V block inside the cache
+int64_t etp_nav_kv_bytes(const etp_planner* p, int B, int L) {
   if (!p) return 0;
-  KvCache k = plan_kv(p, reinterpret_cast<void*>(0x1000), B, L);
-  return p->cfg.n_x > 0 ? (int64_t)(reinterpret_cast<char*>(k.kv[0]) - reinterpret_cast<char*>(0x1000)) : 0;
+  Bump b(nullptr);
+  plan_kv(p, b, B, L);
+  return (int64_t)b.off + 256;
+}
+int64_t etp_nav_kv_offset(const etp_planner* p, int B, int L) {   // byte offset of the first K|V block inside the cache
+  if (!p || p->cfg.n_x == 0) return 0;
+  Bump b(nullptr);
+  return (int64_t)plan_kv(p, b, B, L).kv_off;
 }
 int64_t etp_nav_kv_grad_elems(const etp_planner* p, int B, int L) {
   return p ? (int64_t)p->cfg.n_x * B * L * 2 * p->cfg.hidden : 0;
@@ -1342,7 +1387,8 @@ int64_t etp_nav_kv_grad_elems(const etp_planner* p, int B, int L) {
 int etp_nav_kv_fwd(etp_planner* p, const float* txt, int B, int L, void* kvbuf, etp_stream_t stream) {
   ETP_REQUIRE(p && p->P && txt && kvbuf && B > 0 && L > 0, "bad arguments");
   Ctx c = make_ctx(p, stream);
-  KvCache kc = plan_kv(p, kvbuf, B, L);
+  Bump kb(kvbuf);
+  KvCache kc = plan_kv(p, kb, B, L);
   const int H = c.H, Mt = B * L;
   const void* txtT = txt;
   if (c.dt == ETP_BF16) { ETP_TRY(cast_f32_to_bf16(txt, kc.txtT, (long)Mt * H, c.st)); txtT = kc.txtT; }
@@ -1357,7 +1403,8 @@ int etp_nav_kv_fwd(etp_planner* p, const float* txt, int B, int L, void* kvbuf, 
 int etp_nav_kv_repeat(etp_planner* p, const void* kvbuf, int Bt, int L, int T, void* kvbuf_steps, etp_stream_t stream) {
   ETP_REQUIRE(p && kvbuf && kvbuf_steps && Bt > 0 && L > 0 && T > 0, "bad arguments");
   Ctx c = make_ctx(p, stream);
-  KvCache src = plan_kv(p, const_cast<void*>(kvbuf), Bt, L), dst = plan_kv(p, kvbuf_steps, T * Bt, L);
+  Bump sb(const_cast<void*>(kvbuf)), db(kvbuf_steps);
+  KvCache src = plan_kv(p, sb, Bt, L), dst = plan_kv(p, db, T * Bt, L);
   const long blk = (long)Bt * L * 2 * c.H * (long)c.es;
   for (int l = 0; l < p->cfg.n_x; ++l) ETP_TRY(repeat_block(src.kv[l], dst.kv[l], blk, T, c.st));
   return ETP_OK;
@@ -1375,11 +1422,9 @@ int etp_nav_kv_bwd(etp_planner* p, const float* txt, const void* d_kv, int B, in
                    etp_stream_t stream) {
   ETP_REQUIRE(p && p->P && p->G && txt && d_kv && kvbuf && d_txt && B > 0 && L > 0, "bad arguments");
   Ctx c = make_ctx(p, stream);
-  std::vector<std::function<int()>> pend;
-  std::vector<GemmArgs> wq;
-  if (c.sw != c.st) c.pend = &pend;
-  c.wq = &wq;
-  KvCache kc = plan_kv(p, const_cast<void*>(kvbuf), B, L);
+  SideQueues sq(c);
+  Bump kb(const_cast<void*>(kvbuf));
+  KvCache kc = plan_kv(p, kb, B, L);
   const int H = c.H, Mt = B * L;
   const void* txtT = c.dt == ETP_BF16 ? kc.txtT : (const void*)txt;
   if (p->cfg.n_x == 0) ETP_CHECK_HIP(memset_async(d_txt, 0, (size_t)Mt * H * 4, c.st));
@@ -1405,10 +1450,11 @@ int nav_fwd_impl(etp_planner* p, const float* txt, void* kvbuf, const uint8_t* t
   Bump b(stash);
   NavStash s = plan_nav(p, b, B, L, G);
   const etp_config& cf = p->cfg;
-  const int H = c.H, Mg = B * G, Mt = B * L, ldL = (int)round_up(L, 8);
+  const int H = c.H, Mg = B * G, Mt = B * L;
   const float eps = cf.ln_eps;
-  KvCache kc;
-  if (cached) kc = plan_kv(p, kvbuf, kv_mod > 0 ? kv_mod : B, L);     // kv_mod: the cache holds kv_mod instructions, episode b reads b % kv_mod
+  const CrossDims xd{B, G, L, txt_mask, cached ? kv_mod : 0};
+  Bump kb(kvbuf);                                                    // (no cache: null pointers, never read)
+  const KvCache kc = plan_kv(p, kb, kv_mod > 0 ? kv_mod : B, L);     // kv_mod: the cache holds kv_mod instructions, episode b reads b % kv_mod
   const void* txtT = txt;
   // The text K/V projections of ALL x-layers depend only on the text (M = B*L rows, the largest GEMMs of this entry
   // point), not on the node chain: with a side stream they are issued up front and each layer waits for its own.
@@ -1448,14 +1494,7 @@ int nav_fwd_impl(etp_planner* p, const float* txt, void* kvbuf, const uint8_t* t
     if (kv_side) ETP_CHECK_HIP(stream_wait_event(c.st, kv_ready[l]));
     else if (!cached)
       ETP_TRY(linear_fwd(c, txtT, H, q.kv_w, q.kv_b, t.cross.kv, 2 * H, Mt, 2 * H, H, ETP_ACT_NONE, nullptr, nullptr, 0));
-    void* kv = cached ? kc.kv[l] : t.cross.kv;
-    AttnBuf a{t.cross.q, (long)H, kv, 2L * H, offs(kv, H, c.es), 2L * H, B, G, L, ldL, txt_mask, 0, nullptr, nullptr, nullptr};
-    a.Pd = t.cross.Pd;
-    a.kv_mod = cached ? kv_mod : 0;
-    ETP_TRY(attn_fwd_impl(c.dt, c.nh, a, t.cross.P, t.cross.ctx, H, 0.125f, c.st, att(c, MODE_NAV, l, SITE_X_P)));
-    ETP_TRY(linear_fwd_s(c, t.cross.ctx, H, q.xo_w, q.xo_b, t.cross.s, Mg, H, H, x.f, hid(c, MODE_NAV, l, SITE_X_O)));
-    ETP_TRY(ln_fwd_s(c.dt, t.cross.s, p->pf(q.xln_g), p->pf(q.xln_b), t.cross.y.f, lp(t.cross.y, c.dt), t.cross.st, Mg, H, eps,
-                     c.st));
+    ETP_TRY(cross_att_fwd(c, q, x, t.cross, cached ? kc.kv[l] : t.cross.kv, xd, eps, MODE_NAV, l));
     // graph self attention with the pairwise-distance bias (:391-393)
     ETP_TRY(self_att_fwd(c, q.self, t.cross.y, t.self, B, G, gmask, cf.use_sprels ? dists : nullptr, spw, spb, eps, MODE_NAV, l));
     // bf16 mode: gmap_embeds is the last LayerNorm's own fp32 output (the head and the backward read the bf16 copy y.t);
@@ -1501,23 +1540,21 @@ int nav_bwd_impl(etp_planner* p, const float* d_embeds, const float* d_logits, c
                   d_img && stash && ws && B > 0 && L > 0 && G > 0 && (d_embeds || d_logits),
               "bad arguments");
   Ctx c = make_ctx(p, stream);
-  std::vector<std::function<int()>> pend;
-  std::vector<GemmArgs> wq;
-  if (c.sw != c.st) c.pend = &pend;
-  c.wq = &wq;
+  SideQueues sq(c);
   Bump b(stash);
   NavStash s = plan_nav(p, b, B, L, G);
   Bump wb(ws);
   NavWs n = plan_nav_ws(p, wb, B, L, G);
   const etp_config& cf = p->cfg;
-  const int H = c.H, Mg = B * G, Mt = B * L, ldL = (int)round_up(L, 8);
+  const int H = c.H, Mg = B * G, Mt = B * L;
+  const CrossDims xd{B, G, L, txt_mask, cached ? kv_mod : 0};
   const float* spw = cf.use_sprels ? p->pf(p->sp_w) : nullptr;
   const float* spb = cf.use_sprels ? p->pf(p->sp_b) : nullptr;
   float* dspw = cf.use_sprels ? p->gf(p->sp_w) : nullptr;
   float* dspb = cf.use_sprels ? p->gf(p->sp_b) : nullptr;
   const void* txtT = c.dt == ETP_BF16 ? s.txtT : (const void*)txt;
-  KvCache kc;
-  if (cached) kc = plan_kv(p, const_cast<void*>(kvbuf), kv_mod > 0 ? kv_mod : B, L);
+  Bump kb(const_cast<void*>(kvbuf));
+  const KvCache kc = plan_kv(p, kb, kv_mod > 0 ? kv_mod : B, L);
   const Act xlast = cf.n_x == 0 ? s.x0 : s.layers[cf.n_x - 1].ffn.y;
   float* g = n.g;
   stamp_mark(c.st, 2000);
@@ -1535,30 +1572,16 @@ int nav_bwd_impl(etp_planner* p, const float* d_embeds, const float* d_logits, c
     const XLayerP& q = p->xl[l];
     const XStash& t = s.layers[l];
     const Act x = l == 0 ? s.x0 : s.layers[l - 1].ffn.y;
-    const NavCrossWs& xc = n.cross[l];
-    const BwdWs& w = xc.w;
+    const CrossWs& xc = n.cross[l];
     stamp_mark(c.st, 2010 + 10 * l);
     ETP_TRY(ffn_bwd(c, q.ffn, t.self.y, t.ffn, Mg, g, n.ffn[l], MODE_NAV, l));
     ETP_TRY(self_att_bwd(c, q.self, t.cross.y, t.self, B, G, gmask, cf.use_sprels ? dists : nullptr, spw, spb, dspw, dspb, g,
                          n.self[l], MODE_NAV, l));
-    // cross attention backward
-    const Drop dx = hid(c, MODE_NAV, l, SITE_X_O);
-    ETP_TRY(ln_bwd_chain(c, g, t.cross.s, t.cross.st, q.xln_g, q.xln_b, nullptr, w.t1.f, lp2(c, w.t1, dx), Mg, dx, w.lnp));
-    const void* dso = op2(c, w.t1, dx);
-    ETP_TRY(linear_wgrad(c, dso, H, t.cross.ctx, H, q.xo_w, q.xo_b, Mg, H, H));
-    void* kv = cached ? kc.kv[l] : t.cross.kv;
     // with the cache, dK|dV of this step go straight to the caller's d_kv block of this layer (summed over the rollout's
     // steps by the caller, projected back to the text once by etp_nav_kv_bwd)
     void* dkv_out = cached ? offs(d_kv, (long)l * Mt * 2 * H, c.es) : xc.dkv;
-    AttnBuf a{t.cross.q, (long)H, kv, 2L * H, offs(kv, H, c.es), 2L * H, B, G, L, ldL, txt_mask, 0, nullptr, nullptr, nullptr};
-    a.Pd = t.cross.Pd;
-    a.O = t.cross.ctx; a.ldo = H;
-    a.kv_mod = cached ? kv_mod : 0;
-    ETP_TRY(attn_bwd_proj(c, a, t.cross.P, dso, q.xo_w, w.t2, Mg, xc.dPx, xc.dq, H, dkv_out, 2L * H, offs(dkv_out, H, c.es), 2L * H,
-                          nullptr, nullptr, att(c, MODE_NAV, l, SITE_X_P)));
-    ETP_TRY(linear_wgrad(c, xc.dq, H, x.t, H, q.q_w, q.q_b, Mg, H, H));
     // layer 0 leaves dL/d(node embeddings) = dL/d(gmap_img_fts) in the caller's d_img directly
-    ETP_TRY(linear_dgrad_s(c, xc.dq, H, q.q_w, l == 0 ? d_img : g, Mg, H, H, w.t1.f));
+    ETP_TRY(cross_att_bwd(c, q, x, t.cross, cached ? kc.kv[l] : t.cross.kv, xd, g, l == 0 ? d_img : g, dkv_out, xc, MODE_NAV, l));
     if (cached) { ETP_TRY(flush_side(c)); continue; }
     ETP_TRY(linear_wgrad(c, xc.dkv, 2 * H, txtT, H, q.kv_w, q.kv_b, Mt, 2 * H, H));
     // d_txt (consumed by the text backward right after this entry point) must not queue behind this entry point's weight
@@ -1657,11 +1680,9 @@ int etp_nav_bwd_kv(etp_planner* p, const float* d_embeds, const float* d_logits,
 // The decoder is tied to the word-embedding table: its gradient accumulates into that table's gradient.
 // ======================================================================================
 namespace {
-constexpr int MODE_MLM = 4;
-struct MlmLayerStash { void *q, *kv, *P, *ctx; float* s; float* st; Act y; void* Pd; SelfAttStash self; FfnStash ffn; };
 struct MlmStash {
   void* langT; Act nodes; float* st0;
-  std::vector<MlmLayerStash> layers;
+  std::vector<XStash> layers;
   void *wordT, *hm, *tz, *tg, *hn, *dl; float* stn; float* logits;
 };
 MlmStash plan_mlm(const etp_planner* pl, Bump& b, int Bn, int L, int G, int Nm) {
@@ -1669,22 +1690,15 @@ MlmStash plan_mlm(const etp_planner* pl, Bump& b, int Bn, int L, int G, int Nm) 
   const int dt = c.dtype;
   const size_t es = dtype_size(dt);
   const long Mt = (long)Bn * L, Mg = (long)Bn * G;
-  const int H = c.hidden, ldG = (int)round_up(G, 8), ldL = (int)round_up(L, 8);
+  const int H = c.hidden, ldL = (int)round_up(L, 8);
   const long ldv = round_up(c.vocab, 8);
   MlmStash s;
   s.langT = dt == ETP_BF16 ? b.take(Mt * H * es) : nullptr;
   s.nodes = take_act(b, dt, Mg * H);
   s.st0 = (float*)b.take(Mg * 2 * sizeof(float));
   for (int l = 0; l < c.n_x; ++l) {
-    MlmLayerStash x;
-    x.q = b.take(Mt * H * es);
-    x.kv = b.take(Mg * 2 * H * es);
-    x.P = b.take((size_t)Bn * c.heads * L * ldG * es);
-    x.ctx = b.take(Mt * H * es);
-    x.s = (float*)b.take(Mt * H * 4);
-    x.st = (float*)b.take(Mt * 2 * sizeof(float));
-    x.y = take_act(b, dt, Mt * H);
-    x.Pd = attn_needs_unfused(dt, L, G) ? b.take((size_t)Bn * c.heads * L * ldG * es) : nullptr;
+    XStash x;
+    x.cross = plan_cross(b, dt, Bn, c.heads, L, G, H);
     x.self = plan_self(b, dt, Mt, Bn, c.heads, L, ldL, H);
     x.ffn = plan_ffn(b, dt, Mt, H, c.inter);
     s.layers.push_back(x);
@@ -1699,13 +1713,13 @@ MlmStash plan_mlm(const etp_planner* pl, Bump& b, int Bn, int L, int G, int Nm) 
   s.logits = (float*)b.take((size_t)Nm * ldv * 4);
   return s;
 }
-struct MlmWs { float* g; float* d_nodes; void *d_hn, *d_tg; float* d_hm; std::vector<BwdWs> ffn, self, cross; std::vector<void*> dq, dkv, dPx; };
+struct MlmWs { float* g; float* d_nodes; void *d_hn, *d_tg; float* d_hm; std::vector<BwdWs> ffn, self; std::vector<CrossWs> cross; };
 MlmWs plan_mlm_ws(const etp_planner* pl, Bump& b, int Bn, int L, int G, int Nm) {
   const etp_config& c = pl->cfg;
   const int dt = c.dtype;
   const size_t es = dtype_size(dt);
   const long Mt = (long)Bn * L, Mg = (long)Bn * G;
-  const int H = c.hidden, ldL = (int)round_up(L, 8), ldG = (int)round_up(G, 8);
+  const int H = c.hidden, ldL = (int)round_up(L, 8);
   MlmWs w;
   w.g = (float*)b.take(Mt * H * 4);
   w.d_nodes = (float*)b.take(Mg * H * 4);
@@ -1715,10 +1729,7 @@ MlmWs plan_mlm_ws(const etp_planner* pl, Bump& b, int Bn, int L, int G, int Nm) 
   for (int l = 0; l < c.n_x; ++l) {
     w.ffn.push_back(plan_ws(b, dt, Mt, Bn, c.heads, L, ldL, H, c.inter));
     w.self.push_back(plan_ws(b, dt, Mt, Bn, c.heads, L, ldL, H, c.inter));
-    w.cross.push_back(plan_ws(b, dt, Mt, Bn, c.heads, L, ldL, H, c.inter));
-    w.dq.push_back(b.take(Mt * H * es));
-    w.dkv.push_back(b.take(Mg * 2 * H * es));
-    w.dPx.push_back(b.take((size_t)Bn * c.heads * L * ldG * es));
+    w.cross.push_back(plan_cross_ws(b, dt, Bn, c.heads, L, G, H, c.inter));
   }
   return w;
 }
@@ -1749,7 +1760,8 @@ int etp_mlm_fwd(etp_planner* p, const float* txt, const uint8_t* txt_mask, const
   Bump b(stash);
   MlmStash s = plan_mlm(p, b, B, L, G, Nm);
   const etp_config& cf = p->cfg;
-  const int H = c.H, Mt = B * L, Mg = B * G, ldG = (int)round_up(G, 8);
+  const int H = c.H, Mt = B * L, Mg = B * G;
+  const CrossDims xd{B, L, G, gmask, 0};
   const float eps = cf.ln_eps;
   const long ldv = round_up(cf.vocab, 8);
   Act x;
@@ -1760,16 +1772,12 @@ int etp_mlm_fwd(etp_planner* p, const float* txt, const uint8_t* txt_mask, const
                          p->pf(p->gpos_bb), s.nodes.f, lp(s.nodes, c.dt), s.st0, Mg, H, cf.ang_feat + 3, c.st));
   for (int l = 0; l < cf.n_x; ++l) {
     const XLayerP& q = p->xl[l];
-    MlmLayerStash& t = s.layers[l];
+    XStash& t = s.layers[l];
     // visual_attention with the roles swapped: queries from the text, keys/values from the node inputs
-    ETP_TRY(linear_fwd(c, x.t, H, q.q_w, q.q_b, t.q, H, Mt, H, H, ETP_ACT_NONE, nullptr, nullptr, 0));
-    ETP_TRY(linear_fwd(c, s.nodes.t, H, q.kv_w, q.kv_b, t.kv, 2 * H, Mg, 2 * H, H, ETP_ACT_NONE, nullptr, nullptr, 0));
-    AttnBuf a{t.q, (long)H, t.kv, 2L * H, offs(t.kv, H, c.es), 2L * H, B, L, G, ldG, gmask, 0, nullptr, nullptr, nullptr};
-    a.Pd = t.Pd;
-    ETP_TRY(attn_fwd_impl(c.dt, c.nh, a, t.P, t.ctx, H, 0.125f, c.st, att(c, MODE_MLM, l, SITE_X_P)));
-    ETP_TRY(linear_fwd_s(c, t.ctx, H, q.xo_w, q.xo_b, t.s, Mt, H, H, x.f, hid(c, MODE_MLM, l, SITE_X_O)));
-    ETP_TRY(ln_fwd_s(c.dt, t.s, p->pf(q.xln_g), p->pf(q.xln_b), t.y.f, lp(t.y, c.dt), t.st, Mt, H, eps, c.st));
-    ETP_TRY(self_att_fwd(c, q.lself, t.y, t.self, B, L, txt_mask, nullptr, nullptr, nullptr, eps, MODE_MLM, l));
+    ETP_TRY(linear_fwd(c, x.t, H, q.q_w, q.q_b, t.cross.q, H, Mt, H, H, ETP_ACT_NONE, nullptr, nullptr, 0));
+    ETP_TRY(linear_fwd(c, s.nodes.t, H, q.kv_w, q.kv_b, t.cross.kv, 2 * H, Mg, 2 * H, H, ETP_ACT_NONE, nullptr, nullptr, 0));
+    ETP_TRY(cross_att_fwd(c, q, x, t.cross, t.cross.kv, xd, eps, MODE_MLM, l));
+    ETP_TRY(self_att_fwd(c, q.lself, t.cross.y, t.self, B, L, txt_mask, nullptr, nullptr, nullptr, eps, MODE_MLM, l));
     ETP_TRY(ffn_fwd(c, q.lffn, t.self.y, t.ffn, Mt, eps, MODE_MLM, l));
     x = t.ffn.y;
   }
@@ -1796,16 +1804,14 @@ int etp_mlm_bwd(etp_planner* p, const float* txt, const uint8_t* txt_mask, const
                   B > 0 && L > 0 && G > 0 && Nm > 0,
               "bad arguments");
   Ctx c = make_ctx(p, stream);
-  std::vector<std::function<int()>> pend;
-  std::vector<GemmArgs> wq;
-  if (c.sw != c.st) c.pend = &pend;
-  c.wq = &wq;
+  SideQueues sq(c);
   Bump b(stash);
   MlmStash s = plan_mlm(p, b, B, L, G, Nm);
   Bump wb(ws);
   MlmWs w = plan_mlm_ws(p, wb, B, L, G, Nm);
   const etp_config& cf = p->cfg;
-  const int H = c.H, Mt = B * L, Mg = B * G, ldG = (int)round_up(G, 8);
+  const int H = c.H, Mt = B * L, Mg = B * G;
+  const CrossDims xd{B, L, G, gmask, 0};
   const long ldv = round_up(cf.vocab, 8);
   const void* wordT = c.dt == ETP_BF16 ? s.wordT : (const void*)p->pf(p->word);
   // head: dlogits (saved by the forward CE) -> tied decoder / bias gradients, d hn
@@ -1832,28 +1838,17 @@ int etp_mlm_bwd(etp_planner* p, const float* txt, const uint8_t* txt_mask, const
   ETP_TRY(gather_sum(ETP_F32, w.d_hm, selT_ptr, selT_idx, selT_w, g, Mt, H, 0, c.st));
   for (int l = cf.n_x - 1; l >= 0; --l) {
     const XLayerP& q = p->xl[l];
-    const MlmLayerStash& t = s.layers[l];
+    const XStash& t = s.layers[l];
     Act x;
     if (l == 0) { x.f = const_cast<float*>(txt); x.t = c.dt == ETP_BF16 ? s.langT : (void*)x.f; }
     else x = s.layers[l - 1].ffn.y;
-    const BwdWs& wc = w.cross[l];
+    const CrossWs& wc = w.cross[l];
     ETP_TRY(ffn_bwd(c, q.lffn, t.self.y, t.ffn, Mt, g, w.ffn[l], MODE_MLM, l));
-    ETP_TRY(self_att_bwd(c, q.lself, t.y, t.self, B, L, txt_mask, nullptr, nullptr, nullptr, nullptr, nullptr, g, w.self[l],
+    ETP_TRY(self_att_bwd(c, q.lself, t.cross.y, t.self, B, L, txt_mask, nullptr, nullptr, nullptr, nullptr, nullptr, g, w.self[l],
                          MODE_MLM, l));
-    const Drop dx = hid(c, MODE_MLM, l, SITE_X_O);
-    ETP_TRY(ln_bwd_chain(c, g, t.s, t.st, q.xln_g, q.xln_b, nullptr, wc.t1.f, lp2(c, wc.t1, dx), Mt, dx, wc.lnp));
-    const void* dso = op2(c, wc.t1, dx);
-    ETP_TRY(linear_wgrad(c, dso, H, t.ctx, H, q.xo_w, q.xo_b, Mt, H, H));
-    AttnBuf a{t.q, (long)H, t.kv, 2L * H, offs(t.kv, H, c.es), 2L * H, B, L, G, ldG, gmask, 0, nullptr, nullptr, nullptr};
-    a.Pd = t.Pd;
-    a.O = t.ctx; a.ldo = H;
-    void* dq = w.dq[l]; void* dkv = w.dkv[l];
-    ETP_TRY(attn_bwd_proj(c, a, t.P, dso, q.xo_w, wc.t2, Mt, w.dPx[l], dq, H, dkv, 2L * H, offs(dkv, H, c.es), 2L * H, nullptr,
-                          nullptr, att(c, MODE_MLM, l, SITE_X_P)));
-    ETP_TRY(linear_wgrad(c, dq, H, x.t, H, q.q_w, q.q_b, Mt, H, H));
-    ETP_TRY(linear_dgrad_s(c, dq, H, q.q_w, g, Mt, H, H, wc.t1.f));
-    ETP_TRY(linear_wgrad(c, dkv, 2 * H, s.nodes.t, H, q.kv_w, q.kv_b, Mg, 2 * H, H));
-    ETP_TRY(linear_dgrad_s(c, dkv, 2 * H, q.kv_w, w.d_nodes, Mg, 2 * H, H, nullptr, l == cf.n_x - 1 ? 0 : 1));
+    ETP_TRY(cross_att_bwd(c, q, x, t.cross, t.cross.kv, xd, g, g, wc.dkv, wc, MODE_MLM, l));
+    ETP_TRY(linear_wgrad(c, wc.dkv, 2 * H, s.nodes.t, H, q.kv_w, q.kv_b, Mg, 2 * H, H));
+    ETP_TRY(linear_dgrad_s(c, wc.dkv, 2 * H, q.kv_w, w.d_nodes, Mg, 2 * H, H, nullptr, l == cf.n_x - 1 ? 0 : 1));
     ETP_TRY(flush_side(c));
   }
   ETP_TRY(copy_f32(g, d_txt, (long)Mt * H, c.st));

@@ -173,3 +173,44 @@ def test_dropout_generator_statistics_match_nn_dropout():
             assert abs(r) < 4 / np.sqrt(n - lag), (p, lag, r)
         cols = (out.reshape(512, 768) != 0).mean(0)
         assert abs(cols - (1 - p)).max() < 5 * np.sqrt(p * (1 - p) / 512), (p, cols.min(), cols.max())
+
+
+_BYTES_CONFIGS = {"default": dict(), "rxr": dict(task_type="rxr"), "lang2visn": dict(use_lang2visn_attn=True),
+                  "l1p0x0": dict(num_l_layers=1, num_pano_layers=0, num_x_layers=0),
+                  "nodepth_nosprels": dict(use_depth_embedding=False, graph_sprels=False)}
+_BYTES_SHAPES = ((1, 1, 1, 1), (2, 20, 17, 9), (32, 80, 36, 16), (8, 80, 36, 64), (16, 512, 36, 64))
+
+
+def test_buffer_size_queries_return_the_recorded_bytes():
+    """Callers size their stash / workspace / K-V cache buffers from these host-only queries, and the entry points carve the buffers
+    with the same plan functions: every size and the K/V offset equal tests/golden/planner_buffer_bytes.json exactly (recorded from
+    the build before the planner's plan functions were unified; 5 configurations x 2 dtypes x 5 shapes, MLM sizes at Nm = 7)."""
+    import json
+    import os
+    from etpnav_amd.planner import make_c_config
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "planner_buffer_bytes.json")) as f:
+        want = json.load(f)
+    assert len(want) == len(_BYTES_CONFIGS) * 2 * len(_BYTES_SHAPES)
+    L = _lib.lib()
+    Nm = 7
+    queries = {"etp_txt_stash_bytes": "BL", "etp_txt_ws_bytes": "BL", "etp_pano_stash_bytes": "BV", "etp_pano_ws_bytes": "BV",
+               "etp_nav_stash_bytes": "BLG", "etp_nav_ws_bytes": "BLG", "etp_nav_kv_bytes": "BL", "etp_nav_kv_offset": "BL",
+               "etp_mlm_stash_bytes": "BLGN", "etp_mlm_ws_bytes": "BLGN"}
+    for fn in queries:
+        getattr(L, fn).restype = ctypes.c_int64
+    for name, kw in _BYTES_CONFIGS.items():
+        kw = dict(kw)
+        task = kw.pop("task_type", "r2r")
+        for dt in (torch.float32, torch.bfloat16):
+            c = make_c_config(default_config(task, **kw), dt)
+            h = L.etp_planner_create(ctypes.byref(c))
+            assert h, L.etp_last_error()
+            try:
+                for B, Lt, V, G in _BYTES_SHAPES:
+                    dims = {"B": B, "L": Lt, "V": V, "G": G, "N": Nm}
+                    got = {fn: int(getattr(L, fn)(h, *(dims[d] for d in sig))) for fn, sig in queries.items()
+                           if c.use_lang2visn or not fn.startswith("etp_mlm")}
+                    key = f"{name}/{str(dt).split('.')[-1]}/{B}x{Lt}x{V}x{G}"
+                    assert got == want[key], key
+            finally:
+                L.etp_planner_destroy(h)
