@@ -165,6 +165,9 @@ struct AttnKArgs {
   const void* dctx; long ldd;
   void *dQ, *dK, *dV; long lddq, lddk, lddv;
   float *d_sp_w, *d_sp_b;
+  // streaming kernels only (batched rollout on the text K/V cache): > 0 = episode b reads K / V / key mask of instruction b % kv_mod;
+  // B = stacked episodes (the summed dK/dV kernel walks the B / kv_mod episodes of its instruction)
+  int kv_mod, B;
 };
 
 template <typename T, int BQ, int BKV> struct AttnFwdLds {
@@ -450,7 +453,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnKArgs a) {
 //   backward  P is RECOMPUTED from Q, K and lse (MFMA work is cheap here, HBM traffic is not):
 //             flash_bwd_dq   per (batch, head, 64 queries), loops over key tiles:  D = rowsum(dO*O),  dS = P*(dP*mask - D),
 //                            dQ = alpha dS K;  publishes D next to lse
-//             flash_bwd_dkv  per (batch, head, 128 keys), loops over query tiles:  dV = (P*mask)^T dO,  dK = alpha dS^T Q
+//             flash_bwd_dkv  per (batch, head, 64 keys), loops over query tiles:  dV = (P*mask)^T dO,  dK = alpha dS^T Q
+//   batched rollout (AttnKArgs::kv_mod > 0; the reference re-projects the SAME txt_embeds at every step, ss_trainer_ETP.py:819-822 ->
+//             vilmodel_cmt.py:326-348): T = B / kv_mod steps are stacked along the batch axis and stacked episode b reads K / V / key
+//             mask of instruction b % kv_mod in all three kernels; Q, ctx, lse, D, dO and dQ stay per stacked episode.  dK / dV either
+//             per stacked episode, or SUMMED per instruction inside flash_bwd_dkv (one workgroup per (instruction, head, 64 keys) walks
+//             the query tiles of all T episodes: the sum autograd forms in the shared text tensor, :1055, rounded to bf16 once).
 // Replaces, for Lq or Lk > 128, the batched-GEMM path (scores, probabilities and their gradients through HBM: ~0.9 GB per
 // layer backward at B = 16, L = 512) with three kernels whose HBM traffic is Q, K, V, O, dO in and ctx / dQ, dK, dV out.
 // =========================================================================================================
@@ -528,11 +536,12 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const AttnKArgs a) {
   const int b = bh / a.nh, h = bh % a.nh;
   const int Lq = min(FBQ, a.Lq - q0);
   const T* Qg = reinterpret_cast<const T*>(a.Q) + ((long)b * a.Lq + q0) * a.ldq + h * 64;
-  const T* Kg = reinterpret_cast<const T*>(a.K) + (long)b * a.Lk * a.ldk + h * 64;
-  const T* Vg = reinterpret_cast<const T*>(a.V) + (long)b * a.Lk * a.ldv + h * 64;
+  const int bk = a.kv_mod > 0 ? b % a.kv_mod : b;          // instruction whose keys / values / key mask this episode reads
+  const T* Kg = reinterpret_cast<const T*>(a.K) + (long)bk * a.Lk * a.ldk + h * 64;
+  const T* Vg = reinterpret_cast<const T*>(a.V) + (long)bk * a.Lk * a.ldv + h * 64;
   T* Cg = reinterpret_cast<T*>(a.ctx) + ((long)b * a.Lq + q0) * a.ldc + h * 64;
   float* lse = reinterpret_cast<float*>(a.P) + (long)bh * a.Lq + q0;
-  const uint8_t* km = a.keymask ? a.keymask + (long)b * a.Lk : nullptr;
+  const uint8_t* km = a.keymask ? a.keymask + (long)bk * a.Lk : nullptr;
 
   NatRegs<T, FBKV, 64> rk, rv;
   nat_fetch<T, FBKV, 64>(rk, Kg, a.ldk, min(FBKV, a.Lk), 64, tid);
@@ -686,13 +695,14 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(const AttnKArgs a, co
   const int b = bh / a.nh, h = bh % a.nh;
   const int Lq = min(FBQ, a.Lq - q0);
   const T* Qg = reinterpret_cast<const T*>(a.Q) + ((long)b * a.Lq + q0) * a.ldq + h * 64;
-  const T* Kg = reinterpret_cast<const T*>(a.K) + (long)b * a.Lk * a.ldk + h * 64;
-  const T* Vg = reinterpret_cast<const T*>(a.V) + (long)b * a.Lk * a.ldv + h * 64;
+  const int bk = a.kv_mod > 0 ? b % a.kv_mod : b;
+  const T* Kg = reinterpret_cast<const T*>(a.K) + (long)bk * a.Lk * a.ldk + h * 64;
+  const T* Vg = reinterpret_cast<const T*>(a.V) + (long)bk * a.Lk * a.ldv + h * 64;
   const T* Dg = reinterpret_cast<const T*>(a.dctx) + ((long)b * a.Lq + q0) * a.ldd + h * 64;
   const T* Og = reinterpret_cast<const T*>(O) + ((long)b * a.Lq + q0) * ldo + h * 64;
   const float* lse = reinterpret_cast<const float*>(a.P) + (long)bh * a.Lq + q0;
   float* delta = reinterpret_cast<float*>(a.P) + (long)gridDim.x / a.nq * a.Lq + (long)bh * a.Lq + q0;     // D, behind all lse rows
-  const uint8_t* km = a.keymask ? a.keymask + (long)b * a.Lk : nullptr;
+  const uint8_t* km = a.keymask ? a.keymask + (long)bk * a.Lk : nullptr;
 
   NatRegs<T, FBKV, 64> rk, rv;
   nat_fetch<T, FBKV, 64>(rk, Kg, a.ldk, min(FBKV, a.Lk), 64, tid);
@@ -753,8 +763,16 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(const AttnKArgs a, co
   store_rows64<T, FBQ>(ct, dQg, a.lddq, Lq, tid);
 }
 
-// one workgroup per (batch, head, BKV keys): K/V tile resident, loops over the query tiles
-template <int BKV>
+// one workgroup per (batch, head, BKV keys): K/V tile resident, loops over the query tiles.
+// kv_mod > 0 (batched rollout, T = B / kv_mod steps stacked along the batch axis, episode e reads instruction e % kv_mod):
+//   SUM = false  per-step: the workgroup of stacked episode b reads the tile of instruction b % kv_mod, dK/dV rows stay per episode [B*Lk]
+//   SUM = true   summed:   one workgroup per (INSTRUCTION, head, BKV keys), grid kv_mod * nh * nkv; it walks the query tiles of the T
+//                episodes t*kv_mod + bk that read this tile and keeps adding into the same fp32 dk / dv accumulators, so the sum over the
+//                steps that the shared text tensor needs (ss_trainer_ETP.py:819-822,1055) is rounded to bf16 once, at the single store
+//                into [kv_mod*Lk] rows -- no per-step gradient buffer, no reduction launch.  The walk is ONE flat loop over
+//                (step, query tile) so the register prefetch of the next Q / dO tile crosses episode boundaries like any other step;
+//                lse, D and the dropout element index are the EPISODE's (b*nh + h), the same the forward used.  No LDS beyond SUM = false.
+template <int BKV, bool SUM>
 __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const AttnKArgs a, int nkv) {
   using T = bf16_t;
   using L = FlashLdsT<BKV>;
@@ -764,27 +782,32 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const AttnKArgs a, i
   float* ct = reinterpret_cast<float*>(smem);                       // staging [BKV][68] fp32 over the Q / dO / K tiles
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
   const int i = lane & 15, g = lane >> 4;
-  const int bh = blockIdx.x / nkv, k0 = (blockIdx.x % nkv) * BKV;
-  const int b = bh / a.nh, h = bh % a.nh;
+  const int bh0 = blockIdx.x / nkv, k0 = (blockIdx.x % nkv) * BKV;
+  const int b0 = bh0 / a.nh, h = bh0 % a.nh;                        // b0: the output's batch index (SUM: the instruction)
+  const int bk = SUM ? b0 : (a.kv_mod > 0 ? b0 % a.kv_mod : b0);    // instruction whose K / V / key-mask tile is resident
+  const int nsteps = SUM ? a.B / a.kv_mod : 1;
   const int nk = min(BKV, a.Lk - k0);
-  const T* Qg = reinterpret_cast<const T*>(a.Q) + (long)b * a.Lq * a.ldq + h * 64;
-  const T* Kg = reinterpret_cast<const T*>(a.K) + ((long)b * a.Lk + k0) * a.ldk + h * 64;
-  const T* Vg = reinterpret_cast<const T*>(a.V) + ((long)b * a.Lk + k0) * a.ldv + h * 64;
-  const T* Dg = reinterpret_cast<const T*>(a.dctx) + (long)b * a.Lq * a.ldd + h * 64;
-  const float* lse = reinterpret_cast<const float*>(a.P) + (long)bh * a.Lq;
-  const float* delta = reinterpret_cast<const float*>(a.P) + (long)gridDim.x / nkv * a.Lq + (long)bh * a.Lq;
-  const uint8_t* km = a.keymask ? a.keymask + (long)b * a.Lk : nullptr;
+  const T* Kg = reinterpret_cast<const T*>(a.K) + ((long)bk * a.Lk + k0) * a.ldk + h * 64;
+  const T* Vg = reinterpret_cast<const T*>(a.V) + ((long)bk * a.Lk + k0) * a.ldv + h * 64;
+  const float* stats = reinterpret_cast<const float*>(a.P);         // lse rows of all B*nh (episode, head) pairs, then their D rows
+  const long d_off = (long)a.B * a.nh * a.Lq;
+  const uint8_t* km = a.keymask ? a.keymask + (long)bk * a.Lk : nullptr;
+  const int b_first = SUM ? bk : b0;                                // episode of step t: t * kv_mod + bk
 
   NatRegs<T, FBQ, 64> rq, rd;
-  nat_fetch<T, FBQ, 64>(rq, Qg, a.ldq, min(FBQ, a.Lq), 64, tid);
-  nat_fetch<T, FBQ, 64>(rd, Dg, a.ldd, min(FBQ, a.Lq), 64, tid);
+  nat_fetch<T, FBQ, 64>(rq, reinterpret_cast<const T*>(a.Q) + (long)b_first * a.Lq * a.ldq + h * 64, a.ldq, min(FBQ, a.Lq), 64, tid);
+  nat_fetch<T, FBQ, 64>(rd, reinterpret_cast<const T*>(a.dctx) + (long)b_first * a.Lq * a.ldd + h * 64, a.ldd, min(FBQ, a.Lq), 64, tid);
   nat_load<T, BKV, 64>(kt, Kg, a.ldk, nk, 64, tid);
   nat_load<T, BKV, 64>(vt, Vg, a.ldv, nk, 64, tid);
   float kadd[NT];
   key_terms<NT, BKV>(kadd, km, k0, a.Lk, a.mask_mode, wc, i);
   f32x4_t dk[MTk][2], dv[MTk][2];
   acc_zero(dk); acc_zero(dv);
-  for (int q0 = 0; q0 < a.Lq; q0 += FBQ) {
+  for (int t = 0, q0 = 0; t < nsteps;) {
+    const int b = SUM ? t * a.kv_mod + bk : b0;
+    const int bh = b * a.nh + h;
+    const float* lse = stats + (long)bh * a.Lq;
+    const float* delta = lse + d_off;
     const int nq = min(FBQ, a.Lq - q0);
     float lse_r[MT][4], d_r[MT][4];
     bool row_ok[MT][4];
@@ -800,10 +823,13 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const AttnKArgs a, i
     __syncthreads();                                   // the previous query tile's products are done with qt / dot / tt
     nat_commit<T, FBQ, 64>(qt, rq, tid);
     nat_commit<T, FBQ, 64>(dot, rd, tid);
-    if (q0 + FBQ < a.Lq) {                             // next query tile travels while this one is computed
-      const int nn = min(FBQ, a.Lq - q0 - FBQ);
-      nat_fetch<T, FBQ, 64>(rq, Qg + (long)(q0 + FBQ) * a.ldq, a.ldq, nn, 64, tid);
-      nat_fetch<T, FBQ, 64>(rd, Dg + (long)(q0 + FBQ) * a.ldd, a.ldd, nn, 64, tid);
+    int tn = t, qn = q0 + FBQ;                         // next (step, query tile): the first tile of the next episode after the last
+    if (qn >= a.Lq) { qn = 0; ++tn; }
+    if (tn < nsteps) {                                 // next query tile travels while this one is computed
+      const int bn = SUM ? tn * a.kv_mod + bk : b0;
+      const int nn = min(FBQ, a.Lq - qn);
+      nat_fetch<T, FBQ, 64>(rq, reinterpret_cast<const T*>(a.Q) + ((long)bn * a.Lq + qn) * a.ldq + h * 64, a.ldq, nn, 64, tid);
+      nat_fetch<T, FBQ, 64>(rd, reinterpret_cast<const T*>(a.dctx) + ((long)bn * a.Lq + qn) * a.ldd + h * 64, a.ldd, nn, 64, tid);
     }
     __syncthreads();
     f32x4_t sc[MT][NT], dp[MT][NT];
@@ -818,10 +844,11 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const AttnKArgs a, i
     acc_to_tile<MT, NT, BKV>(dp, tt, PP, wr, wc, i, g);            // dS over the same tile
     __syncthreads();
     tile_mma<T, MTk, 2, FBQ / 32, true, true, PP, PQ>(dk, tt, wr * (BKV / 2), qt, wc * 32, lane);      // dK += dS^T Q
+    t = tn; q0 = qn;
   }
   __syncthreads();
-  T* dKg = reinterpret_cast<T*>(a.dK) + ((long)b * a.Lk + k0) * a.lddk + h * 64;
-  T* dVg = reinterpret_cast<T*>(a.dV) + ((long)b * a.Lk + k0) * a.lddv + h * 64;
+  T* dKg = reinterpret_cast<T*>(a.dK) + ((long)b0 * a.Lk + k0) * a.lddk + h * 64;
+  T* dVg = reinterpret_cast<T*>(a.dV) + ((long)b0 * a.Lk + k0) * a.lddv + h * 64;
   acc_to_lds(dv, ct, 68, wr * (BKV / 2), wc * 32, 1.0f, lane);
   __syncthreads();
   store_rows64<T, BKV>(ct, dVg, a.lddv, nk, tid);
@@ -868,6 +895,7 @@ static AttnKArgs make_args(int nh, const AttnBuf& a, float alpha) {
   k.Q = a.Q; k.K = a.K; k.V = a.V; k.ldq = a.ldq; k.ldk = a.ldk; k.ldv = a.ldv;
   k.ldS = a.ldS; k.nh = nh; k.Lq = a.Lq; k.Lk = a.Lk;
   k.keymask = a.keymask; k.mask_mode = a.mask_mode; k.dist = a.dist; k.sp_w = a.sp_w; k.sp_b = a.sp_b; k.alpha = alpha;
+  k.kv_mod = a.kv_mod; k.B = a.B;
   return k;
 }
 
@@ -885,10 +913,12 @@ bool attn_flash_ok(int dt, const AttnBuf& a, long ldc) {
 static int flash_attr() {
   ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(flash_fwd_kernel), FlashLds::TOTAL));      // per device (launch.h)
   ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dq_kernel), FlashLds::TOTAL));
-  ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dkv_kernel<FBKV2>), FlashLdsT<FBKV2>::TOTAL));
+  ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dkv_kernel<FBKV2, false>), FlashLdsT<FBKV2>::TOTAL));
+  ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dkv_kernel<FBKV2, true>), FlashLdsT<FBKV2>::TOTAL));
   return ETP_OK;
 }
 int attn_flash_fwd(int nh, const AttnBuf& a, void* P, void* ctx, long ldc, float alpha, hipStream_t st, Drop drop) {
+  ETP_REQUIRE(a.kv_mod == 0 || (a.kv_mod > 0 && a.B % a.kv_mod == 0), "kv_mod must divide the number of stacked episodes");
   ETP_TRY(flash_attr());
   AttnKArgs k = make_args(nh, a, alpha);
   k.drop = drop;
@@ -901,6 +931,8 @@ int attn_flash_fwd(int nh, const AttnBuf& a, void* P, void* ctx, long ldc, float
 int attn_flash_bwd(int nh, const AttnBuf& a, const void* P, const void* dctx, long ldd, void* dQ, long lddq, void* dK, long lddk,
                    void* dV, long lddv, float alpha, hipStream_t st, Drop drop) {
   ETP_REQUIRE(a.O != nullptr, "the streaming attention backward needs the forward output (AttnBuf::O)");
+  ETP_REQUIRE(a.kv_mod == 0 || (a.kv_mod > 0 && a.B % a.kv_mod == 0), "kv_mod must divide the number of stacked episodes");
+  ETP_REQUIRE(!a.dkv_sum || a.kv_mod > 0, "summed dK/dV needs per-episode K/V indirection (kv_mod > 0)");
   ETP_TRY(flash_attr());
   AttnKArgs k = make_args(nh, a, alpha);
   k.drop = drop;
@@ -910,7 +942,12 @@ int attn_flash_bwd(int nh, const AttnBuf& a, const void* P, const void* dctx, lo
   const int nkv = (a.Lk + FBKV2 - 1) / FBKV2;
   ETP_LAUNCH(flash_bwd_dq_kernel, dim3(a.B * nh * k.nq), dim3(256), FlashLds::TOTAL, st, k, a.O, a.ldo);
   ETP_CHECK_LAUNCH("flash_bwd_dq");
-  ETP_LAUNCH(flash_bwd_dkv_kernel<FBKV2>, dim3(a.B * nh * nkv), dim3(256), FlashLdsT<FBKV2>::TOTAL, st, k, nkv);
+  if (a.dkv_sum) {      // one workgroup per (instruction, head, key tile): the sum over the stacked steps stays in its accumulators
+    ETP_LAUNCH((flash_bwd_dkv_kernel<FBKV2, true>), dim3(a.kv_mod * nh * nkv), dim3(256), FlashLdsT<FBKV2>::TOTAL, st, k, nkv);
+    ETP_CHECK_LAUNCH("flash_bwd_dkv_sum");
+    return ETP_OK;
+  }
+  ETP_LAUNCH((flash_bwd_dkv_kernel<FBKV2, false>), dim3(a.B * nh * nkv), dim3(256), FlashLdsT<FBKV2>::TOTAL, st, k, nkv);
   ETP_CHECK_LAUNCH("flash_bwd_dkv");
   return ETP_OK;
 }

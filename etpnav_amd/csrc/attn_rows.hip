@@ -738,6 +738,8 @@ int attn_rows_bwd(int nh, const AttnBuf& a, const void* P, const void* dctx, lon
                   ((uintptr_t)dctx | (uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV) % 16 == 0,
               "gradient operands of the register-resident attention must be 16-byte aligned");
   ETP_REQUIRE(proj_w == nullptr || attn_rows_proj_ok(proj_k, proj_w, proj_ldw), "fused out-projection dgrad: unsupported reduction length / alignment");
+  ETP_REQUIRE(!a.dkv_sum, "dK/dV summed per instruction (AttnBuf::dkv_sum) needs the streaming attention kernels (bf16, an axis > 128): "
+                          "the register-resident kernels write them per stacked episode");
   if (skip_attn("bwd")) return ETP_OK;
   RowArgs k = make_row_args(nh, a, const_cast<void*>(P), alpha, drop);
   k.dO = (const bf16_t*)dctx; k.ldd = ldd;

@@ -297,6 +297,40 @@ int etp_attn_bwd(const etp_attn_bwd_desc* d, etp_stream_t s) {
                        d->dV, d->lddv, d->f.alpha, d->d_sp_w, d->d_sp_b, (hipStream_t)s);
 }
 
+// per-episode K/V indirection at operator level: the families whose kernels carry kv_mod (2 register-resident, 3 streaming)
+static int kv_family(const char* who, const etp_attn_desc& f, int kv_mod, int sum_steps, AttnBuf& ab) {
+  if (kv_mod <= 0 || f.B <= 0 || f.B % kv_mod != 0)
+    return fail(ETP_ERR_INVALID, std::string(who) + ": kv_mod must be positive and divide B");
+  if (sum_steps != 0 && sum_steps != 1) return fail(ETP_ERR_INVALID, std::string(who) + ": sum_steps must be 0 or 1");
+  ab = to_buf(f);
+  ab.kv_mod = kv_mod;
+  ab.dkv_sum = sum_steps == 1;
+  const int fam = attn_family(f.dtype, ab, f.ldc);
+  if (fam != ATTN_FAMILY_ROWS && fam != ATTN_FAMILY_FLASH)
+    return fail(ETP_ERR_INVALID, std::string(who) + ": per-episode K/V indirection needs the register-resident or the streaming kernels "
+                                                    "(bf16, dist NULL beyond 128, aligned operands, switches on); replicate K / V instead");
+  if (fam == ATTN_FAMILY_ROWS && sum_steps)
+    return fail(ETP_ERR_INVALID, std::string(who) + ": the register-resident kernels (both axes <= 128) write dK / dV per stacked episode: "
+                                                    "sum_steps must be 0");
+  return ETP_OK;
+}
+int etp_attn_fwd_kv(const etp_attn_desc* d, int kv_mod, etp_stream_t s) {
+  ETP_REQUIRE(d && d->Q && d->K && d->V && d->P && d->ctx, "null pointer");
+  ETP_REQUIRE(d->ldS >= d->Lk && d->ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+  AttnBuf ab;
+  ETP_TRY(kv_family("etp_attn_fwd_kv", *d, kv_mod, 0, ab));
+  return attn_fwd_impl(d->dtype, d->heads, ab, d->P, d->ctx, d->ldc, d->alpha, (hipStream_t)s);
+}
+int etp_attn_bwd_kv(const etp_attn_bwd_desc* d, int kv_mod, int sum_steps, etp_stream_t s) {
+  ETP_REQUIRE(d && d->f.Q && d->f.K && d->f.V && d->f.P && d->f.ctx && d->dctx && d->dQ && d->dK && d->dV, "null pointer");
+  ETP_REQUIRE(d->f.ldS >= d->f.Lk && d->f.ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+  AttnBuf ab;
+  ETP_TRY(kv_family("etp_attn_bwd_kv", d->f, kv_mod, sum_steps, ab));
+  ab.O = d->f.ctx; ab.ldo = d->f.ldc;
+  return attn_bwd_impl(d->f.dtype, d->f.heads, ab, d->f.P, d->dctx, d->ldd, d->dP, d->dQ, d->lddq, d->dK, d->lddk,
+                       d->dV, d->lddv, d->f.alpha, d->d_sp_w, d->d_sp_b, (hipStream_t)s);
+}
+
 int etp_attn_fwd_qkv(const etp_attn_desc* d, const void* x, int64_t ldx, const void* w_qkv, int64_t ldw, const float* b_qkv, etp_stream_t s) {
   ETP_REQUIRE(d && d->Q && d->K && d->V && d->P && d->ctx && x && w_qkv, "null pointer");
   ETP_REQUIRE(d->ldS >= d->Lk && d->ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");

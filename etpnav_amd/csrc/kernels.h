@@ -84,8 +84,12 @@ struct AttnBuf {
   void* Pd = nullptr;      // unfused path only: second [B,heads,Lq,ldS] buffer for the DROPPED probabilities (training mode)
   const void* O = nullptr; long ldo = 0;   // backward only: the forward output (streaming kernels: D = rowsum(dO * O))
   // > 0 (round 6, batched rollout on the text K/V cache): episode b reads the keys / values / key mask of instruction b % kv_mod
-  // (Q, ctx and every gradient stay per episode).  Register-resident kernels only (attn_rows.hip); the other families refuse it.
+  // (Q, ctx and every gradient stay per episode).  Register-resident (attn_rows.hip) and streaming kernels (attn.hip); the LDS-tile
+  // and batched-GEMM families refuse it.
   int kv_mod = 0;
+  // backward with kv_mod > 0: dK / dV are SUMMED per instruction over the B / kv_mod stacked steps inside the kernel and have
+  // kv_mod*Lk rows (not B*Lk).  Streaming kernels only; the register-resident family refuses it.
+  bool dkv_sum = false;
 };
 // shapes the fused kernels do not take (the batched-GEMM path runs them and needs AttnBuf::Pd for dropout)
 // (bf16 with Lq or Lk > 128 normally runs the streaming kernels instead; the second buffer is still planned so that

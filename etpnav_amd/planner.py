@@ -325,9 +325,11 @@ class _NavKVStepsFn(torch.autograd.Function):
 
 class _NavCachedFn(torch.autograd.Function):
     """forward_navigation on the text K/V cache.  steps_T > 1 (batched rollout, round 6): `kv` / `txt_masks` hold the Bt = B / steps_T
-    instructions ONCE and stacked episode e reads instruction e % Bt inside the cross-attention kernels (etp_nav_fwd_kv_steps /
-    etp_nav_bwd_kv_steps) -- no replicated cache; the backward sums d_kv over the steps (etp_nav_kv_sum_steps), the sum the reference's
-    shared txt_embeds tensor accumulates through autograd (ss_trainer_ETP.py:819-822,1055)."""
+    instructions ONCE and stacked episode e reads instruction e % Bt inside the cross-attention kernels (etp_nav_fwd_kv_steps) -- no
+    replicated cache.  The backward needs d_kv summed over the steps, the sum the reference's shared txt_embeds tensor accumulates
+    through autograd (ss_trainer_ETP.py:819-822,1055): etp_nav_kv_steps_mode 1 (register-resident kernels, axes <= 128) writes it per
+    step (etp_nav_bwd_kv_steps) and reduces it (etp_nav_kv_sum_steps); mode 2 (streaming kernels, RxR's 512-token instructions) forms the
+    sum inside the dK/dV kernel (etp_nav_bwd_kv_steps_sum): no per-step buffer, no reduction."""
 
     @staticmethod
     def forward(ctx, anchor, eng: Engine, drop, kv, L, txt_masks, step_ids, img_fts, pos_fts, gmasks, visited, dists, steps_T=1):
@@ -363,7 +365,11 @@ class _NavCachedFn(torch.autograd.Function):
         d_img = torch.empty(B, G, H, dtype=torch.float32, device=eng.device)
         ws = eng.ws(("nav", B, L, G), eng.L.etp_nav_ws_bytes(eng.handle, B, L, G))
         eng.set_dropout(ctx.drop)
-        if T > 1:
+        if T > 1 and eng.L.etp_nav_kv_steps_mode(eng.handle, B, L, G, B // T) == 2:
+            check(eng.L.etp_nav_bwd_kv_steps_sum(eng.handle, ptr(d_out), ptr(d_logits), ctx.cache, ptr(txt_masks), ptr(step_ids),
+                                                 ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, B // T, ptr(d_kv),
+                                                 ptr(d_img), ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd_kv_steps_sum")
+        elif T > 1:
             n_x, _, H2 = ctx.kv_shape
             d_kv_steps = torch.empty(n_x, B * L, H2, dtype=eng.tdtype, device=eng.device)
             check(eng.L.etp_nav_bwd_kv_steps(eng.handle, ptr(d_out), ptr(d_logits), ctx.cache, ptr(txt_masks), ptr(step_ids),
@@ -409,7 +415,7 @@ class GlocalTextPathNavCMT(nn.Module):
         # text K/V cache across rollout steps; off = the reference's per-step re-projection
         self.cache_text_kv = False
         self.batch_steps_kv = True        # forward_navigation_steps: project the text keys/values once, not T times
-        self.kv_indirection = True        # ... and let the cross-attention kernels read instruction e % B (no replicated cache; bf16, axes <= 128)
+        self.kv_indirection = True        # ... and let the cross-attention kernels read instruction e % B (no replicated cache; bf16)
         self._kv_cache = None
         self.drop_env_prob = 0.0          # >0 fuses the policy's drop_env (Policy_ViewSelection_ETP.py:102,345) into forward_panorama
         self._drop_seed = int(torch.initial_seed()) & 0xFFFFFFFF
@@ -615,9 +621,9 @@ class GlocalTextPathNavCMT(nn.Module):
 
         Text keys/values (self.batch_steps_kv, default on): the K|V projections of the B instructions are computed ONCE
         (etp_nav_kv_fwd, shared with cache_text_kv's per-step calls), replicated for the T stacked steps by a copy
-        (etp_nav_kv_repeat; round 6: not even that where the register-resident attention kernels run -- bf16, both axes <= 128 --
-        the stacked episode e reads instruction e % B inside the kernels, etp_nav_fwd_kv_steps) and their gradient is summed over
-        the steps (etp_nav_kv_sum_steps) before ONE projection back to
+        (etp_nav_kv_repeat; not even that in bf16, where the register-resident or the streaming attention kernels run: the
+        stacked episode e reads instruction e % B inside the kernels, etp_nav_fwd_kv_steps) and their gradient is summed over
+        the steps (etp_nav_kv_sum_steps; inside the streaming dK/dV kernel for instructions beyond 128 tokens) before ONE projection back to
         the text (etp_nav_kv_bwd) -- instead of projecting T * B * L stacked text rows forward and backward in every x-layer,
         which is the re-projection of vilmodel_cmt.py:326-328 the reference repeats per step.  batch_steps_kv = False keeps
         the stacked re-projection (same results up to the rounding of the summed bf16 key/value gradients)."""
@@ -643,9 +649,10 @@ class GlocalTextPathNavCMT(nn.Module):
             t = torch.float32
             L = txt_embeds.shape[1]
             kv = self._text_kv(eng, txt_embeds)
-            # bf16 with both axes <= 128 (every R2R-CE shape): the cross-attention kernels read instruction e % B themselves; otherwise
-            # (fp32 parity mode, RxR's 512-token instructions) the cache is replicated for the stacked steps (etp_nav_kv_repeat)
-            indirect = T > 1 and eng.tdtype == torch.bfloat16 and L <= 128 and Gm <= 128 and self.kv_indirection
+            # bf16 (register-resident kernels for the R2R-CE shapes, streaming kernels for RxR's 512-token instructions): the
+            # cross-attention kernels read instruction e % B themselves; otherwise (fp32 parity mode, a kernel family switched off) the
+            # cache is replicated for the stacked steps (etp_nav_kv_repeat).  The library decides, from the family it would dispatch.
+            indirect = T > 1 and self.kv_indirection and eng.L.etp_nav_kv_steps_mode(eng.handle, T * B, L, Gm, B) != 0
             if indirect:
                 kv_in, masks_in, steps_T = kv, txt_masks.to(torch.bool).contiguous(), T
             else:

@@ -164,6 +164,20 @@ typedef struct etp_attn_bwd_desc {
   float* d_sp_w; float* d_sp_b; /* accumulated, or NULL */
 } etp_attn_bwd_desc;
 int etp_attn_bwd(const etp_attn_bwd_desc* d, etp_stream_t stream);
+/* The same two calls with PER-EPISODE K/V INDIRECTION (the batched rollout: T = B / kv_mod steps stacked along the batch axis share the
+ * kv_mod instructions; the reference re-projects the same txt_embeds at every step, ss_trainer_ETP.py:819-822 -> BertOutAttention
+ * vilmodel_cmt.py:326-348): K and V have kv_mod*Lk rows, keymask is [kv_mod, Lk], and stacked episode b reads instruction b % kv_mod
+ * inside the kernels.  Q, ctx, P, dctx and dQ stay per stacked episode ([B*Lq] rows); B % kv_mod == 0.
+ *   sum_steps == 0   dK / dV per stacked episode, B*Lk rows: the same bits as etp_attn_fwd / etp_attn_bwd on K, V and masks replicated
+ *                    B / kv_mod times
+ *   sum_steps == 1   dK / dV SUMMED over the B / kv_mod episodes of each instruction, kv_mod*Lk rows (what autograd accumulates into the
+ *                    shared txt_embeds, ss_trainer_ETP.py:1055): the streaming dK/dV kernel keeps the sum in its fp32 accumulators and
+ *                    rounds once.  Deterministic (no atomics).
+ * Served by families 2 (register-resident; sum_steps == 0 only) and 3 (streaming) of etp_attn_family; any other family (fp32, dist
+ * beyond 128, a switch turned off, unaligned operands), sum_steps == 1 on family 2 or B % kv_mod != 0 returns ETP_ERR_INVALID and
+ * launches nothing. */
+int etp_attn_fwd_kv(const etp_attn_desc* d, int kv_mod, etp_stream_t stream);
+int etp_attn_bwd_kv(const etp_attn_bwd_desc* d, int kv_mod, int sum_steps, etp_stream_t stream);
 /* The same backward with the OUT-PROJECTION's input gradient folded in (round 6): `d->dctx` is dL/d(dense output) [B*Lq, heads*64]
  * (row stride ldd) of BertSelfOutput.dense / BertOutAttention's output dense / MHA out_proj (vilmodel_cmt.py:150-154, 325-352;
  * common/transformer.py:138-142), `w_out` that projection's weight [heads*64 (out)][ldw] in the operand dtype; each (batch, head)
@@ -441,9 +455,19 @@ int etp_nav_bwd_kv(etp_planner* p, const float* d_gmap_embeds /*or NULL*/, const
 /* The same two calls with PER-EPISODE INDIRECTION instead of the replicated copy (round 6; N1): B = T * Bt stacked episodes, `kv_cache`
  * (etp_nav_kv_bytes(p, Bt, L)) and `txt_masks` [Bt, L] hold the Bt instructions once, and episode e reads the keys / values / key mask
  * of instruction e % Bt inside the cross-attention kernels (vilmodel_cmt.py:326-328 with the same txt_embeds at every step,
- * ss_trainer_ETP.py:819-822).  d_kv is still per stacked episode [n_x][B*L][2H] (the caller sums it over the steps with
- * etp_nav_kv_sum_steps).  bf16 with L and G <= 128 (the register-resident attention kernels); otherwise ETP_ERR_INVALID: use
- * etp_nav_kv_repeat + the calls above. */
+ * ss_trainer_ETP.py:819-822).
+ *   etp_nav_kv_steps_mode     host only, launches nothing: how this shape is served under the current switches, from the kernel family
+ *                             of the cross-attention descriptor (etp_attn_family's helper):
+ *                               0  no indirection (fp32, a switch off): use etp_nav_kv_repeat + the calls above
+ *                               1  register-resident kernels (bf16, L and G <= 128): etp_nav_bwd_kv_steps, d_kv per stacked episode
+ *                                  [n_x][B*L][2H], summed over the steps by the caller with etp_nav_kv_sum_steps
+ *                               2  streaming kernels (bf16, L or G > 128, e.g. RxR's 512-token instructions): etp_nav_bwd_kv_steps_sum,
+ *                                  d_kv [n_x][Bt*L][2H] already summed over the steps inside the dK/dV kernel (the sum autograd forms in
+ *                                  the shared txt_embeds, ss_trainer_ETP.py:1055) -- no per-step gradient buffer, no reduction launch
+ *   etp_nav_fwd_kv_steps      every shape whose mode is not 0; otherwise ETP_ERR_INVALID
+ *   etp_nav_bwd_kv_steps      mode 1; mode 2 fails with ETP_ERR_INVALID and names etp_nav_bwd_kv_steps_sum
+ *   etp_nav_bwd_kv_steps_sum  mode 2; the arguments of etp_nav_bwd_kv_steps except for the shape of d_kv */
+int etp_nav_kv_steps_mode(const etp_planner* p, int B, int L, int G, int Bt);
 int etp_nav_fwd_kv_steps(etp_planner* p, const void* kv_cache, const uint8_t* txt_masks, const int64_t* gmap_step_ids,
                          const float* gmap_img_fts, const float* gmap_pos_fts, const uint8_t* gmap_masks,
                          const uint8_t* gmap_visited_masks, const float* gmap_pair_dists, int B, int L, int G, int Bt,
@@ -453,6 +477,11 @@ int etp_nav_bwd_kv_steps(etp_planner* p, const float* d_gmap_embeds /*or NULL*/,
                          const uint8_t* gmap_masks, const uint8_t* gmap_visited_masks, const float* gmap_pair_dists, int B, int L,
                          int G, int Bt, void* d_kv /*[n_x][B*L][2H], overwritten*/, float* d_gmap_img_fts, void* stash, void* ws,
                          etp_stream_t stream);
+int etp_nav_bwd_kv_steps_sum(etp_planner* p, const float* d_gmap_embeds /*or NULL*/, const float* d_logits /*or NULL*/,
+                             const void* kv_cache, const uint8_t* txt_masks, const int64_t* gmap_step_ids, const float* gmap_pos_fts,
+                             const uint8_t* gmap_masks, const uint8_t* gmap_visited_masks, const float* gmap_pair_dists, int B,
+                             int L, int G, int Bt, void* d_kv /*[n_x][Bt*L][2H], overwritten*/, float* d_gmap_img_fts, void* stash,
+                             void* ws, etp_stream_t stream);
 
 /* Device-side graph-input assembly: everything RLTrainer._nav_gmap_variable computes on the host
  * besides the node embeddings (ss_trainer_ETP.py:344-417) -- all-pairs shortest paths over the visited-node graph

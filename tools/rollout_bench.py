@@ -8,7 +8,8 @@ Three ways of issuing the same work (identical outputs and gradients: tests/test
                     projects the T-fold stacked text rows to keys/values in every x-layer (round 3's form)
     batched_copy    forward_navigation_steps on the K/V cache: one projection, replicated for the stacked steps by a copy (round 4's form)
     batched         the same with per-episode indirection (round 6): stacked episode e reads instruction e % B inside the
-                    cross-attention kernels, no replicated cache (bf16, axes <= 128)
+                    cross-attention kernels, no replicated cache (bf16; beyond 128 tokens, e.g. --L 512 --B 16, the streaming
+                    kernels also sum d_kv over the steps themselves: no per-step gradient buffer, no reduction launch)
 
     python tools/rollout_bench.py [--B 8] [--L 80] [--T 5,10,15] [--G 16] [--dtype bf16] [--iters 20]
 Prints one JSON object (ms per episode fwd+bwd, episodes/s) -> profiles/r03_rollout_bench.json.
