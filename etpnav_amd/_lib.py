@@ -227,6 +227,28 @@ class option:
         return False
 
 
+class profiled:
+    """``with _lib.profiled() as p: <eager GEMM launches>`` -- bracket them with the per-launch profiler (etp_prof_reset,
+    etp_prof_enable(1) ... etp_prof_report, etp_prof_enable(0)); afterwards ``p.launches`` maps the name of every kernel instance
+    that ran (e.g. ``gemm_dma<bf16,f32,NT,64x64,s3>``) to its launch count.  The operator tests assert it."""
+
+    def __enter__(self):
+        L = lib()
+        self.launches: Dict[str, int] = {}
+        L.etp_prof_reset()
+        L.etp_prof_enable(1)
+        return self
+
+    def __exit__(self, *exc):
+        L = lib()
+        ents = (ProfEntry * 32)()
+        n = L.etp_prof_report(ents, 32)
+        L.etp_prof_enable(0)
+        L.etp_prof_reset()
+        self.launches = {e.name.decode(): int(e.launches) for e in list(ents)[:max(n, 0)]}
+        return False
+
+
 def force_gemm_tile(tile: str = "") -> None:
     """Tuning aid: force a tile class of gemm.hip's kernels for the following launches ("" / "auto" = the library's own choice).
     The mm32 family is consulted BEFORE gemm.hip's tile choice (csrc/gemm_mm32.hip::mm32_class), so forcing a gemm.hip class

@@ -580,6 +580,11 @@ static int prepare_args(int dtype, int c_dtype, int ta, int tb, const GemmArgs& 
   ETP_REQUIRE(g0.out_mode != 2 || c_dtype == ETP_F32, "atomic accumulation needs an fp32 C");
   ETP_REQUIRE(g0.ksplit == 1 || g0.out_mode == 2, "split-K needs atomic accumulation");
   ETP_REQUIRE(g0.drop.p == 0.f || (g0.ksplit == 1 && nbatch == 1), "epilogue dropout needs an unsplit, unbatched product");
+  // Every split of a reduction runs the whole epilogue on its partial sum (only the bias is tied to split 0), and no kernel offsets R or Z
+  // by the batch index: a residual, an activation or its operand on such a product would be added once per split / read from batch entry
+  // 0.  No caller combines them (planner.hip: the split weight gradient and the batched attention products are plain).
+  ETP_REQUIRE((g0.ksplit == 1 && nbatch == 1) || (g0.R == nullptr && g0.Z == nullptr && g0.act == ETP_ACT_NONE),
+              "a residual, an activation or Z needs an unsplit, unbatched product");
   ETP_REQUIRE(g0.a_colsum == nullptr || (ta && tb && gemm_uses_dma(dtype, g0.K, g0.ksplit)),
               "a_colsum needs the TN LDS-DMA kernel (check gemm_uses_dma first)");
   ETP_REQUIRE(dtype != ETP_F32 || c_dtype == ETP_F32, "fp32 operands need an fp32 C");
@@ -588,11 +593,14 @@ static int prepare_args(int dtype, int c_dtype, int ta, int tb, const GemmArgs& 
     const bool xcd_on = opt_on(OPT_GEMM_XCD, true);
     g.xcd_map = xcd_on;
   }
-  {  // the vectorised epilogue needs 8-column chunks to stay in-bounds and 16-byte aligned
+  {  // the vectorised epilogue handles whole, 16-byte aligned 8-column chunks: with N % 8 != 0 its last chunk of a row would overwrite
+     // columns N .. round_up(N, 8) - 1 of C (and of Z), which belong to the caller -- such products take the scalar epilogue
+     // (every nn.Linear product of the planner has N % 8 == 0; the unfused attention path's S = Q.K^T and dP = dctx.V^T products have
+     // N = Lk and move to the scalar epilogue when Lk % 8 != 0 -- softmax_fwd / softmax_bwd write the pad of P and dP themselves)
     const size_t cs = dtype_size(c_dtype);
-    bool ok = (g.ldc % 8 == 0) && (g.ldc >= round_up(g.N, 8)) && ((uintptr_t)g.C % 16 == 0) && ((g.sCo * cs) % 16 == 0) &&
+    bool ok = (g.N % 8 == 0) && (g.ldc % 8 == 0) && (g.ldc >= g.N) && ((uintptr_t)g.C % 16 == 0) && ((g.sCo * cs) % 16 == 0) &&
               ((g.sCi * cs) % 16 == 0);
-    if (g.bias) ok = ok && ((uintptr_t)g.bias % 16 == 0) && (g.N % 8 == 0);
+    if (g.bias) ok = ok && ((uintptr_t)g.bias % 16 == 0);
     if (g.R) ok = ok && (g.ldr % 8 == 0) && ((uintptr_t)g.R % 16 == 0) && (g.ldr >= round_up(g.N, 8));
     if (g.Z) ok = ok && (g.ldz % 8 == 0) && ((uintptr_t)g.Z % 16 == 0) && (g.ldz >= round_up(g.N, 8));
     if (g.out_mode == 2) ok = false;   // atomics: lane-consecutive fp32 columns (row-major scalar path) coalesce best

@@ -156,7 +156,9 @@ __device__ __forceinline__ void epi_prefetch(EpiPre<T, TC, BM, BN, NTH>& pre, co
 
 // Epilogue shared by every GEMM kernel, second half: the fp32 accumulator tile sits in LDS as [BM][BN + 4] (staged by the
 // caller, followed by a barrier); each thread combines whole 8-column chunks with bias / activation / dropout / residual /
-// old C and stores them as 16-byte vectors.
+// old C and stores them as 16-byte vectors.  A chunk is tested (`col < N`) and then read and written WHOLE: g.vec_epilogue therefore
+// implies N % 8 == 0 (prepare_args, gemm.hip) -- with a ragged N the last chunk of a row would overwrite columns N .. round_up(N, 8) - 1
+// of C and Z, which the contract of include/etpnav_hip.h leaves to the caller; such products take the scalar path below.
 // NCT > 1: NCT such tiles lie behind one another ([NCT][BM][BN + 4]: the partial sums of an intra-workgroup split of the
 // reduction, gemm_mm32.hip KS = 2) and are added as they are read.
 // FIX >= 0 (gemm_mm32.hip mm32::tile): the epilogue's variant is a COMPILE-TIME constant -- activation code in bits 0-7, bias in bit 8, residual in

@@ -59,7 +59,29 @@ int etp_option_list(char* out, int cap);                     /* "NAME=value\n" p
 
 /* C[m,n] = epi(alpha * sum_k A[m,k]*B[n,k]); replaces every nn.Linear / torch.matmul on the path
  * (vilmodel_cmt.py:108-110,117,133,151,178,190,326-328,335,348; common/transformer.py:138,140-142) and their
- * autograd backward (dgrad / wgrad).  trans_a/trans_b = 1 means the operand is stored [K][rows]. */
+ * autograd backward (dgrad / wgrad).  trans_a/trans_b = 1 means the operand is stored [K][rows].
+ *
+ * The contract in one place (tests/test_gemm_kernels_gpu.py holds every kernel instance to it):
+ *   v = alpha * sum_k A[m,k] B[n,k] + bias[n]     fp32 accumulation, alpha BEFORE the bias
+ *   y = act(v)  [* Z for the backward forms]  + R[m,n]          R is added after the activation
+ *   C = y (out_mode 0) | C + y, added in fp32 and rounded once (out_mode 1) | atomicAdd(C, y) (out_mode 2)
+ * Written: C[m, n] for m < M, n < N, nothing else: columns N .. ldc - 1 of a row, rows beyond M and whatever surrounds a C that
+ *   is a slice of a wider buffer are left alone (N % 8 != 0 takes a one-element-per-thread epilogue for that reason).  Z[m, n]
+ *   for the same m, n under ETP_ACT_GELU (v, operand dtype) and ETP_ACT_GELU_SAVEGRAD (gelu'(v); IEEE half in bf16 mode).
+ * Accumulated: C under out_mode 1 / 2; a_colsum[m] += sum_k A[m,k] ALWAYS accumulates, whatever out_mode says.
+ * Read only: A, B, bias, R, Z under ETP_ACT_GELU_BWD / RELU_BWD (operand dtype) / MUL_Z (IEEE half in bf16 mode).
+ * K == 0 is accepted: C = epi(0).
+ * Alignment: A and B 16-byte aligned, lda / ldb and the A / B batch strides multiples of a 16-byte chunk (8 bf16, 4 fp32); a
+ *   transposed operand's leading dimension covers its row count rounded up to that chunk.  C, R, Z and bias may sit anywhere:
+ *   16-byte aligned bases with leading dimensions that are multiples of 8 (and N % 8 == 0) take the vectorised epilogue,
+ *   everything else the scalar one, with equal results.
+ * Which fields combine (everything else returns ETP_ERR_INVALID before anything is launched):
+ *   (trans_a, trans_b) in {(0,0), (0,1), (1,1)};  dtype ETP_F32 needs c_dtype ETP_F32;
+ *   out_mode 2 needs c_dtype ETP_F32;  ksplit > 1 needs out_mode 2 (the bias is added by the first split only);
+ *   R, Z and an activation other than ETP_ACT_NONE need ksplit == 1 and batch == 1: every split would run the epilogue on its
+ *     partial sum, and R / Z carry no batch stride;
+ *   an activation other than ETP_ACT_NONE / ETP_ACT_RELU needs Z;
+ *   a_colsum needs trans_a = trans_b = 1 and a reduction (per split) of whole 128-byte slabs, at least two of them. */
 typedef struct etp_gemm_desc {
   const void* A; const void* B; void* C;
   int32_t M, N, K;
@@ -72,8 +94,10 @@ typedef struct etp_gemm_desc {
   int32_t ksplit;           /* >1: split the reduction, needs out_mode 2 */
   float alpha;
   const float* bias;        /* [N] or NULL */
-  const void* R; int64_t ldr; /* residual added after the activation, dtype T, or NULL */
-  void* Z; int64_t ldz;     /* aux tensor for the activation epilogues, dtype T */
+  const void* R; int64_t ldr; /* residual added after the activation, in the OUTPUT dtype (c_dtype: fp32 with bf16 operands and an
+                               * fp32 C), or NULL; unsplit, unbatched products only */
+  void* Z; int64_t ldz;     /* aux tensor for the activation epilogues, operand dtype (IEEE half for ETP_ACT_GELU_SAVEGRAD /
+                             * ETP_ACT_MUL_Z in bf16 mode); unsplit, unbatched products only */
   int32_t act;              /* ETP_ACT_* */
   int32_t out_mode;         /* 0 store, 1 C += v, 2 atomicAdd (fp32 C) */
   float* a_colsum;          /* TN products (weight gradients) only, or NULL: a_colsum[m] += sum_k A[m,k] -- the bias gradient
