@@ -187,6 +187,11 @@ void stamp_mark(hipStream_t st, int tag) {
 }
 }  // namespace etp
 
+// the row kernels read and write four elements per lane (load4 / store4: 8 bytes bf16, 16 bytes fp32; fp32 parameters as float4);
+// NULL (an optional pointer the entry point allows) passes
+template <typename... P> static bool aligned16(P... p) { return ((... | (uintptr_t)p) % 16) == 0; }
+template <typename... P> static bool aligned_rows(int dtype, P... p) { return ((... | (uintptr_t)p) % (dtype == ETP_BF16 ? 8 : 16)) == 0; }
+
 extern "C" {
 
 const char* etp_version(void) { return "etpnav_hip 0.1.0 (gfx950)"; }
@@ -233,32 +238,38 @@ int etp_gemm_group(const etp_gemm_desc* d, int n, etp_stream_t stream) {
 
 int etp_colsum(int dtype, const void* dy, int64_t ld, float* db, int M, int N, etp_stream_t s) {
   ETP_REQUIRE(dy && db, "null pointer");
+  ETP_REQUIRE(aligned_rows(dtype, dy), "dy must be aligned to four elements (8 bytes bf16 / 16 bytes fp32)");
   return colsum(dtype, dy, ld, db, M, N, (hipStream_t)s);
 }
 int etp_ln_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* stats, int M, int H, float eps,
                etp_stream_t s) {
   ETP_REQUIRE(x && gamma && beta && y, "null pointer");
+  ETP_REQUIRE(aligned_rows(dtype, x, y) && aligned16(gamma, beta), "x / y must be aligned to four elements, gamma / beta to 16 bytes");
   return ln_fwd(dtype, x, gamma, beta, y, stats, M, H, eps, (hipStream_t)s);
 }
 int etp_ln_bwd(int dtype, const void* dy, const void* x, const float* stats, const float* gamma, const void* add, void* dx,
                float* dgamma, float* dbeta, int M, int H, etp_stream_t s) {
   ETP_REQUIRE(dy && x && stats && gamma && dx && ((dgamma == nullptr) == (dbeta == nullptr)), "null pointer");
+  ETP_REQUIRE(aligned_rows(dtype, dy, x, add, dx) && aligned16(gamma), "dy / x / add / dx must be aligned to four elements, gamma to 16 bytes");
   return ln_bwd(dtype, dy, x, stats, gamma, add, dx, dgamma, dbeta, M, H, (hipStream_t)s);
 }
 int etp_ln_stream_fwd(int dtype, const float* x, const float* gamma, const float* beta, float* y, void* y_lp, float* stats, int M,
                       int H, float eps, etp_stream_t s) {
   ETP_REQUIRE(x && gamma && beta && (y || y_lp), "null pointer");
+  ETP_REQUIRE(aligned16(x, gamma, beta, y) && aligned_rows(dtype, y_lp), "x / gamma / beta / y must be 16-byte aligned, y_lp to four elements");
   return ln_fwd_s(dtype, x, gamma, beta, y, y_lp, stats, M, H, eps, (hipStream_t)s);
 }
 int etp_ln_stream_bwd(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add,
                       float* dx, void* dx_lp, float* dgamma, float* dbeta, int M, int H, etp_stream_t s) {
   ETP_REQUIRE(dy && x && stats && gamma && (dx || dx_lp) && ((dgamma == nullptr) == (dbeta == nullptr)), "null pointer");
+  ETP_REQUIRE(aligned16(dy, x, gamma, add, dx) && aligned_rows(dtype, dx_lp), "dy / x / gamma / add / dx must be 16-byte aligned, dx_lp to four elements");
   return ln_bwd_s(dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, M, H, (hipStream_t)s);
 }
 int64_t etp_ln_bwd_part_bytes(int M, int H) { return (M > 0 && H > 0) ? (int64_t)ln_bwd_part_bytes(M, H) : 0; }
 int etp_ln_stream_bwd_stage1(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add,
                              float* dx, void* dx_lp, float* dgamma, float* dbeta, float* part, int M, int H, etp_stream_t s) {
   ETP_REQUIRE(dy && x && stats && gamma && (dx || dx_lp) && dgamma && dbeta && part, "null pointer");
+  ETP_REQUIRE(aligned16(dy, x, gamma, add, dx) && aligned_rows(dtype, dx_lp), "dy / x / gamma / add / dx must be 16-byte aligned, dx_lp to four elements");
   return ln_bwd_s(dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, M, H, (hipStream_t)s, drop_none(), part);
 }
 int etp_ln_part_reduce(const float* part, int M, int H, float* dgamma, float* dbeta, etp_stream_t s) {
@@ -437,6 +448,7 @@ int etp_grad_sqnorm_masked(const float* grads, int64_t n, const uint8_t* mask, f
 int etp_gather_sum(int dtype, const void* src, const int32_t* ptr, const int32_t* idx, const float* w, void* out, int N, int H,
                    int accumulate, etp_stream_t s) {
   ETP_REQUIRE(src && ptr && idx && w && out, "null pointer");
+  ETP_REQUIRE(aligned_rows(dtype, src, out), "src / out must be aligned to four elements (8 bytes bf16 / 16 bytes fp32)");
   return gather_sum(dtype, src, ptr, idx, w, out, N, H, accumulate, (hipStream_t)s);
 }
 int etp_cast_f32_to_bf16(const float* src, void* dst, int64_t n, etp_stream_t s) {

@@ -127,6 +127,8 @@ int adamw_step(float* p, float* g, float* m, float* v, void* shadow, long n_shad
   ETP_REQUIRE(p && g && m && v && n > 0 && n % 4 == 0, "arena pointers / length (multiple of 4) required");
   ETP_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0, "arenas must be 16-byte aligned");
   ETP_REQUIRE((c.step >= 1 || step_dev != nullptr) && c.beta1 >= 0.f && c.beta1 < 1.f && c.beta2 >= 0.f && c.beta2 < 1.f && c.eps >= 0.f, "bad hyper-parameters");
+  // clipping without the norm used to train UNCLIPPED without a word (the kernel tests sumsq != nullptr)
+  ETP_REQUIRE(!(c.max_norm > 0.f) || sumsq != nullptr, "max_norm > 0 needs the squared gradient norm (sumsq)");
   ETP_REQUIRE(shadow == nullptr || (n_shadow >= 0 && n_shadow <= n && n_shadow % 4 == 0 && (uintptr_t)shadow % 8 == 0), "bad shadow region");
   AdamwK k;
   k.lr = c.lr; k.beta1 = c.beta1; k.beta2 = c.beta2; k.eps = c.eps; k.wd = c.weight_decay;

@@ -109,14 +109,18 @@ int etp_gemm(const etp_gemm_desc* d, etp_stream_t stream);
  * of which fills 256 CUs alone.  Every K must be a multiple of the 128-byte slab (64 bf16 / 32 fp32) and >= 2 slabs. */
 int etp_gemm_group(const etp_gemm_desc* d, int n, etp_stream_t stream);
 
-/* db[n] += sum_m dY[m,n]  (bias gradient of every nn.Linear). */
+/* db[n] += sum_m dY[m,n]  (bias gradient of every nn.Linear).  db ACCUMULATES.  N % 4 == 0 and ld % 4 == 0; dy aligned to four
+ * elements (8 bytes bf16, 16 bytes fp32); columns [N, ld) are never read.  Anything else: ETP_ERR_INVALID, nothing launched. */
 int etp_colsum(int dtype, const void* dy, int64_t ld, float* db, int M, int N, etp_stream_t stream);
 
-/* y = LayerNorm(x); stats[row] = {mean, rstd}.  BertLayerNorm / nn.LayerNorm: vilmodel_cmt.py:59,147,186,459-478,
+/* y = LayerNorm(x); stats[row] = {mean, rstd} (stats may be NULL).  x / y in `dtype`, gamma / beta / stats fp32.  H in {256, 512, 768,
+ * 1024}.  x / y / dy / add / dx must be aligned to four elements (8 bytes bf16, 16 bytes fp32), gamma / beta to 16 bytes (every LayerNorm
+ * entry point below checks the same and returns ETP_ERR_INVALID before anything is launched).  BertLayerNorm / nn.LayerNorm: vilmodel_cmt.py:59,147,186,459-478,
  * 571,656; common/transformer.py:144-145; common/ops.py:19-23. */
 int etp_ln_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* stats, int M, int H,
                float eps, etp_stream_t stream);
-/* dx = LNbwd(dy) (+ add if non-NULL); dgamma/dbeta accumulated atomically. */
+/* dx = LNbwd(dy) (+ add if non-NULL), OVERWRITTEN; dgamma / dbeta ACCUMULATED atomically -- pass both or neither (a mixed NULL pair
+ * is refused).  stats: the forward's {mean, rstd} rows. */
 int etp_ln_bwd(int dtype, const void* dy, const void* x, const float* stats, const float* gamma, const void* add, void* dx,
                float* dgamma, float* dbeta, int M, int H, etp_stream_t stream);
 
@@ -221,7 +225,10 @@ int etp_ln_stream_bwd(int dtype, const float* dy, const float* x, const float* s
                       float* dx, void* dx_lp, float* dgamma, float* dbeta, int M, int H, etp_stream_t stream);
 /* The same with the two-stage parameter-gradient reduction the planner uses: stage 1 (on `stream`) writes per-workgroup
  * column sums to `part` (etp_ln_bwd_part_bytes(M, H) bytes), stage 2 (on `reduce_stream`, ordered after stage 1 by the
- * caller when the streams differ) adds them into dgamma / dbeta. */
+ * caller when the streams differ) adds them into dgamma / dbeta.
+ * etp_ln_bwd_part_bytes = 2*H*4 bytes per stage-1 workgroup: ceil(ceil(M/4) / rounds) workgroups, rounds = ceil(ceil(M/4) / cap), cap =
+ * 1024 or the LNBWD_GRID switch clamped to [1, 1024].  Change the switch between the size query and the two stages and the sizes no
+ * longer agree.  Stage 1 needs dgamma, dbeta and part non-NULL (it does not touch dgamma / dbeta); stage 2 only reads part. */
 int64_t etp_ln_bwd_part_bytes(int M, int H);
 int etp_ln_stream_bwd_stage1(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add,
                              float* dx, void* dx_lp, float* dgamma, float* dbeta, float* part, int M, int H, etp_stream_t stream);
@@ -272,16 +279,21 @@ int etp_sap_tail_bwd(int dtype, const float* dlogits, const void* r, const float
 
 /* F.cross_entropy(reduction='sum', ignore_index) ss_trainer_ETP.py:892 scaled by `scale` (:1055):
  * *loss = scale*sum_b nll_b (stored, not accumulated) ; dlogits = scale*(softmax - onehot) (0 on ignored rows); dlogits may
- * be NULL. */
+ * be NULL.  One workgroup; labels must be ignore_index or in [0, G); a -inf logit no label points at gets an exactly zero gradient;
+ * with every row ignored *loss and dlogits are exactly 0. */
 int etp_sap_ce(const float* logits, const int64_t* labels, float* loss, float* dlogits, int B, int G, float scale,
                int64_t ignore_index, etp_stream_t stream);
 
 /* out[n,:] (+)= sum_{j in [ptr[n],ptr[n+1])} w[j]*src[idx[j],:] — node aggregation (ss_trainer_ETP.py:838-839,
- * graph_utils.py:272-276, pretrain vilmodel.py:585-619) and, with the transposed CSR, its backward. */
+ * graph_utils.py:272-276, pretrain vilmodel.py:585-619) and, with the transposed CSR, its backward.  src / out in `dtype` (bf16: the
+ * row is accumulated in fp32 and rounded once), aligned to four elements; H in {256, 512, 768}; ptr has N + 1 entries; accumulate != 0
+ * adds onto what out holds; rows >= N are not touched. */
 int etp_gather_sum(int dtype, const void* src, const int32_t* ptr, const int32_t* idx, const float* w, void* out, int N, int H,
                    int accumulate, etp_stream_t stream);
 
+/* Round-to-nearest-even (NaN stays NaN); src and dst 16-byte aligned, any n. */
 int etp_cast_f32_to_bf16(const float* src, void* dst, int64_t n, etp_stream_t stream);
+/* dst[i] = float(src[i]) * scale and p[i] *= scale: one fp32 rounding per element; scalar accesses, natural alignment, any n. */
 int etp_cast_bf16_to_f32(const void* src, float* dst, int64_t n, float scale, etp_stream_t stream);
 int etp_scale_f32(float* p, int64_t n, float scale, etp_stream_t stream);
 
@@ -303,7 +315,11 @@ int etp_scale_f32(float* p, int64_t n, float scale, etp_stream_t stream);
  * the only value whose meaning changed for an old caller is exactly 2.
  * shadow (nullable): bf16 copy written for elements [0, n_shadow).  skip (nullable, device int32): non-zero -> leave
  * p/m/v/shadow untouched (GradScaler's skipped step); gradients are still zeroed when zero_grads != 0.
- * sumsq / skip are produced by etp_grad_sqnorm (both ACCUMULATE: zero them first).  n % 4 == 0, 16-byte aligned. */
+ * sumsq / skip are produced by etp_grad_sqnorm (both ACCUMULATE: zero them first).  n % 4 == 0, 16-byte aligned.
+ * decay_mask holds ceil(n / 64) bytes: when n % 64 != 0 the last byte covers the partial block (the kernels read byte e >> 6 of element
+ * e and nothing behind it).  n_shadow % 4 == 0 and 0 <= n_shadow <= n.  max_norm > 0 REQUIRES sumsq (it used to train unclipped without
+ * a word when sumsq was NULL); 0 <= beta < 1; step >= 1 unless a device counter is given.  A refused call launches nothing.
+ * zero_grads == 0 leaves the gradients as they are.  A frozen block's gradient is zeroed like any other. */
 typedef struct {
   float lr, beta1, beta2, eps, weight_decay;
   int32_t step;
@@ -317,12 +333,15 @@ int etp_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
                    int zero_grads, etp_stream_t stream);
 /* The same with the optimizer's step count kept ON THE DEVICE: *step_counter is incremented only when the update is applied
  * (skip == NULL or *skip == 0) and the bias corrections use it -- GradScaler.step() does not call optimizer.step() on
- * overflow, so state['step'] must not advance on a skipped step (ss_trainer_ETP.py:504-506).  cfg->step is ignored. */
+ * overflow, so state['step'] must not advance on a skipped step (ss_trainer_ETP.py:504-506).  cfg->step is ignored.  The bias
+ * corrections are then formed on the device in fp32 (powf): at beta2 = 0.999 and t = 1 that is a relative error of up to ~1e-4 in the
+ * update (2^-24 * beta^t / (1 - beta^t)), against 1e-7 for etp_adamw_step, which forms them on the host in double. */
 int etp_adamw_step_counted(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow, int64_t n_shadow,
                            const uint8_t* decay_mask, int64_t n, const etp_adamw_cfg* cfg, const float* sumsq, const int32_t* skip,
                            int zero_grads, int32_t* step_counter, etp_stream_t stream);
+/* *sumsq += sum g^2, *nonfinite += number of NaN / +-inf values (nonfinite may be NULL); n % 4 == 0, grads 16-byte aligned. */
 int etp_grad_sqnorm(const float* grads, int64_t n, float* sumsq, int32_t* nonfinite, etp_stream_t stream);
-/* The same, leaving out the blocks whose mask byte (layout of decay_mask above) has bit 1 set: frozen parameters have no .grad in
+/* The same, leaving out the blocks whose mask byte (layout of decay_mask above, ceil(n / 64) bytes) is 2 or 3: frozen parameters have no .grad in
  * the reference, so clip_grad_norm_ / GradScaler's non-finite scan never see them. */
 int etp_grad_sqnorm_masked(const float* grads, int64_t n, const uint8_t* mask, float* sumsq, int32_t* nonfinite,
                            etp_stream_t stream);
