@@ -425,6 +425,16 @@ int etp_sap_ce(const float* logits, const int64_t* labels, float* loss, float* d
   ETP_REQUIRE(logits && labels && loss, "null pointer");
   return sap_ce(logits, labels, loss, dlogits, B, G, scale, (long)ignore_index, (hipStream_t)s);
 }
+int etp_ring_attn_fwd(int dtype, const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* ctx,
+                      int64_t ldc, int B, int neighbor, float alpha, etp_stream_t s) {
+  return ring_attn_fwd(dtype, Q, (long)ldq, K, (long)ldk, V, (long)ldv, ctx, (long)ldc, B, neighbor, alpha, (hipStream_t)s);
+}
+int etp_waypoint_tail(const float* logits, int B, int max_pred, float sigma_x, float sigma_y, const float* uniforms, float* heat,
+                      float* nms_map, int32_t* cand_count, int32_t* cand_angle, int32_t* cand_dist, int32_t* cand_img_cw,
+                      int32_t* cand_img_ccw, int32_t* samp_angle, int32_t* samp_dist, etp_stream_t s) {
+  return waypoint_tail(logits, B, max_pred, sigma_x, sigma_y, uniforms, heat, nms_map, cand_count, cand_angle, cand_dist, cand_img_cw,
+                       cand_img_ccw, samp_angle, samp_dist, (hipStream_t)s);
+}
 int etp_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow, int64_t n_shadow,
                    const uint8_t* decay_mask, int64_t n, const etp_adamw_cfg* cfg, const float* sumsq, const int32_t* skip,
                    int zero_grads, etp_stream_t s) {

@@ -70,6 +70,14 @@ int zero_f32(float* dst, long n, hipStream_t st);
 int repeat_block(const void* src, void* dst, long bytes, int T, hipStream_t st);            // dst[t][.] = src[.], t < T
 int sum_steps(int dtype, const void* src, void* dst, long n, int steps, hipStream_t st);   // dst[i] = sum_t src[t][i], fp32 accumulation
 
+// waypoint.hip: the waypoint predictor's neighbourhood attention and its heat-map tail (forward only)
+int ring_attn_fwd(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* ctx, long ldc, int B,
+                  int neighbor, float alpha, hipStream_t st);
+int waypoint_tail(const float* logits, int B, int max_pred, float sigma_x, float sigma_y, const float* uniforms, float* heat,
+                  float* nms_map, int32_t* cand_count, int32_t* cand_angle, int32_t* cand_dist, int32_t* cand_img_cw,
+                  int32_t* cand_img_ccw, int32_t* samp_angle, int32_t* samp_dist, hipStream_t st);
+int waypoint_roll(const float* in, float* out, int B, hipStream_t st);     // out[b, a, d] = in[b, (a + 5) % 120, d]
+
 // optim.hip: fused AdamW (+ bf16 shadow refresh + gradient zeroing) and the gradient norm / non-finite scan
 int adamw_step(float* p, float* g, float* m, float* v, void* shadow, long n_shadow, const uint8_t* decay_mask, long n,
                const etp_adamw_cfg& c, const float* sumsq, const int32_t* skip, int zero_grads, hipStream_t st,

@@ -1,9 +1,10 @@
 """Habitat-free mirror of the planner-facing part of vlnce_baselines/models/Policy_ViewSelection_ETP.py.
 
 ``ETP.forward(mode=...)`` keeps the reference's keyword names and dispatch (Policy_ViewSelection_ETP.py:157-170,
-:344-358) for the three planner modes; the waypoint / perception modes depend on habitat, CLIP and DD-PPO encoders and
-stay with the reference (out of scope).  ``PolicyViewSelectionETP`` mirrors ILPolicy (models/policy.py:
-12-19): it just holds ``.net``.
+:344-358) for the three planner modes.  ``mode='waypoint'`` (:172-342) runs the native waypoint head (etpnav_amd/waypoint.py)
+once the user has attached the reference's perception encoders as ``net.depth_encoder`` / ``net.rgb_encoder`` (habitat, CLIP
+and the DD-PPO ResNet stay out of scope); without them it raises NotImplementedError.
+``PolicyViewSelectionETP`` mirrors ILPolicy (models/policy.py:12-19): it just holds ``.net``.
 """
 from __future__ import annotations
 
@@ -11,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .vlnbert_init import get_vlnbert_models
+from .waypoint import pano_constants, waypoint_mode
 
 
 class ETP(nn.Module):
@@ -21,6 +23,12 @@ class ETP(nn.Module):
         # fused: the p=0.4 feature dropout rides in forward_panorama's operand cast (and its mask is recomputed for the
         # img_linear weight gradient and d rgb_fts) instead of a separate elementwise pass over [B,V,F] + a saved mask
         self.fuse_drop_env = fuse_drop_env
+        # mode='waypoint': the reference's VlnResnetDepthEncoder / CLIPEncoder (:118-138), supplied by the user; None = not attached
+        self.depth_encoder = None
+        self.rgb_encoder = None
+        self.space_pool_depth = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), nn.Flatten(start_dim=2))   # :125
+        self.space_pool_rgb = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), nn.Flatten(start_dim=2))     # :139
+        self.pano_img_idxes, self.pano_angle_fts = pano_constants()                                    # :141-143
 
     def forward(self, mode=None, txt_ids=None, txt_masks=None, txt_embeds=None, waypoint_predictor=None,
                 observations=None, in_train=True, rgb_fts=None, dep_fts=None, loc_fts=None, nav_types=None,
@@ -39,8 +47,11 @@ class ETP(nn.Module):
             return self.vln_bert.forward_navigation(txt_embeds, txt_masks, gmap_vp_ids, gmap_step_ids, gmap_img_fts,
                                                     gmap_pos_fts, gmap_masks, gmap_visited_masks, gmap_pair_dists)
         if mode == "waypoint":
-            raise NotImplementedError("mode='waypoint' (CLIP + DD-PPO encoders + waypoint predictor) stays in the reference; "
-                                      "this package replaces the planner modes only")
+            if self.depth_encoder is None or self.rgb_encoder is None:
+                raise NotImplementedError("mode='waypoint' needs the reference's CLIP + DD-PPO encoders: attach them as "
+                                          "net.depth_encoder / net.rgb_encoder (INTEGRATION.md); this package replaces the "
+                                          "waypoint predictor and the heat-map tail behind them")
+            return waypoint_mode(self, waypoint_predictor, observations, in_train)
         raise NotImplementedError(mode)
 
 

@@ -1,0 +1,294 @@
+"""Native waypoint head: the mirror of vlnce_baselines/waypoint_pred/TRM_net.py (BinaryDistPredictor_TRM) and of the heat-map tail of
+vlnce_baselines/models/Policy_ViewSelection_ETP.py:220-318, on the HIP engine of csrc/waypoint_engine.hip and the two kernels of
+csrc/waypoint.hip.
+
+    ring_attn(q, k, v, ctx, B, neighbor, alpha)      etp_ring_attn_fwd on torch tensors (operator level)
+    waypoint_tail(logits, max_pred, sigma, uniforms) etp_waypoint_tail -> CandidateTable (device)
+    BinaryDistPredictorTRM                            nn.Module with the reference's state-dict names; forward -> logits [B,120,12];
+                                                      candidates(logits, in_train, generator) -> CandidateTable
+    waypoint_mode(net, predictor, observations, in_train)   the body of ETP.forward(mode='waypoint')
+
+The predictor is frozen and runs in eval() (ss_trainer_ETP.py:201-202): forward only, parameters do not require gradients.
+There is no CPU fallback: without the built library, or without a GPU, the compute paths raise.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from copy import deepcopy
+from typing import Dict, List, NamedTuple, Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from ._lib import check, ptr
+
+NUM_ANGLES, NUM_IMGS, NUM_CLASSES = 120, 12, 12           # Policy_ViewSelection_ETP.py:176-178
+MAX_PREDICTIONS, NMS_SIGMA = 5, (7.0, 5.0)                # :233-236
+HEATMAP_OFFSET = 5                                        # TRM_net.py:20
+
+
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _require_gpu(t: torch.Tensor, what: str):
+    if t.device.type != "cuda":
+        raise _lib.EtpError(f"{what}: the waypoint kernels need an MI355X (cuda/hip device); no CPU fallback exists")
+
+
+# ---- operator level -----------------------------------------------------------------------------------------------------------
+def ring_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ctx: torch.Tensor, B: int, neighbor: int = 1,
+              alpha: float = 0.125) -> torch.Tensor:
+    """ctx[B*12, :768] = neighbourhood attention of q / k / v (rows [B*12, ld], 2-D tensors or column slices of one packed
+    [B*12, 2304] buffer; stride(1) == 1).  Writes into `ctx` (same dtype, bf16 or fp32) and returns it."""
+    _require_gpu(q, "ring_attn")
+    dt = {torch.float32: _lib.ETP_F32, torch.bfloat16: _lib.ETP_BF16}[q.dtype]
+    for t in (q, k, v, ctx):
+        assert t.dim() == 2 and t.stride(1) == 1 and t.dtype == q.dtype and t.device == q.device
+    check(_lib.lib().etp_ring_attn_fwd(dt, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                       ctx.data_ptr(), ctx.stride(0), B, neighbor, alpha, _stream()), "etp_ring_attn_fwd")
+    return ctx
+
+
+class CandidateTable(NamedTuple):
+    """Device-side result of the tail.  `table` is ONE int32 tensor [7, B, max_pred] whose rows are count (column 0), angle, dist,
+    img_cw, img_ccw, samp_angle, samp_dist: a single copy brings everything the host loops need."""
+    heat: torch.Tensor
+    nms_map: torch.Tensor
+    table: torch.Tensor
+    sampled: bool
+
+    @property
+    def count(self): return self.table[0, :, 0]
+    @property
+    def angle(self): return self.table[1]
+    @property
+    def dist(self): return self.table[2]
+    @property
+    def img_cw(self): return self.table[3]
+    @property
+    def img_ccw(self): return self.table[4]
+    @property
+    def samp_angle(self): return self.table[5]
+    @property
+    def samp_dist(self): return self.table[6]
+
+
+def waypoint_tail(logits: torch.Tensor, max_pred: int = MAX_PREDICTIONS, sigma=NMS_SIGMA,
+                  uniforms: Optional[torch.Tensor] = None) -> CandidateTable:
+    """logits [B,120,12] fp32 (rolled) -> heat, nms map and the candidate table (etp_waypoint_tail)."""
+    _require_gpu(logits, "waypoint_tail")
+    assert logits.dtype == torch.float32 and logits.shape[1:] == (NUM_ANGLES, NUM_CLASSES)
+    logits = logits.contiguous()
+    B = logits.shape[0]
+    heat = torch.empty_like(logits)
+    nms_map = torch.empty_like(logits)
+    table = torch.full((7, B, max(max_pred, 1)), -1, dtype=torch.int32, device=logits.device)
+    if uniforms is not None:
+        uniforms = uniforms.to(device=logits.device, dtype=torch.float32).contiguous()
+        assert tuple(uniforms.shape) == (B, max_pred)
+    cnt = torch.empty(max(B, 1), dtype=torch.int32, device=logits.device)
+    check(_lib.lib().etp_waypoint_tail(ptr(logits), B, max_pred, float(sigma[0]), float(sigma[1]), ptr(uniforms), ptr(heat),
+                                       ptr(nms_map), ptr(cnt), table[1].data_ptr(), table[2].data_ptr(), table[3].data_ptr(),
+                                       table[4].data_ptr(), table[5].data_ptr() if uniforms is not None else None,
+                                       table[6].data_ptr() if uniforms is not None else None, _stream()), "etp_waypoint_tail")
+    table[0, :, 0] = cnt[:B]
+    return CandidateTable(heat, nms_map, table, uniforms is not None)
+
+
+# ---- the predictor --------------------------------------------------------------------------------------------------------------
+class _Node(nn.Module):
+    """Plain container reproducing the reference's module tree (state-dict names)."""
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError("container module; call BinaryDistPredictorTRM.forward")
+
+
+def param_table(dtype: torch.dtype = torch.float32):
+    """[(reference state-dict name, shape, arena offset)] of the engine; needs the built library, not a GPU."""
+    L = _lib.lib()
+    h = L.etp_waypoint_create(_lib.ETP_BF16 if dtype == torch.bfloat16 else _lib.ETP_F32)
+    if not h:
+        raise _lib.EtpError("etp_waypoint_create: " + L.etp_last_error().decode())
+    try:
+        info = _lib.ParamInfo()
+        out = []
+        for i in range(L.etp_waypoint_param_count(h)):
+            check(L.etp_waypoint_param_info(h, i, ctypes.byref(info)), "etp_waypoint_param_info")
+            out.append((info.name.decode(), tuple(int(info.shape[k]) for k in range(info.ndim)), int(info.offset)))
+        return out
+    finally:
+        L.etp_waypoint_destroy(h)
+
+
+class BinaryDistPredictorTRM(nn.Module):
+    """TRM_net.py:9-88 on the HIP engine.  Parameters are views of one flat fp32 arena under the reference's names (the unused
+    visual_merge / mergefeats_LayerNorm included), so ``load_state_dict(torch.load(cwp_fn)['predictor']['state_dict'])`` is strict."""
+
+    def __init__(self, hidden_dim: int = 768, n_classes: int = 12, device=None, dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        assert hidden_dim == 768 and n_classes == 12, "the shipped predictor: hidden 768, 12 distance classes"
+        assert dtype in (torch.float32, torch.bfloat16)
+        self.num_angles, self.num_imgs, self.n_classes = NUM_ANGLES, NUM_IMGS, NUM_CLASSES
+        self.TRM_LAYER, self.TRM_NEIGHBOR, self.HEATMAP_OFFSET = 2, 1, HEATMAP_OFFSET
+        self.L = _lib.lib()
+        self.compute_dtype = dtype
+        self.handle = self.L.etp_waypoint_create(_lib.ETP_BF16 if dtype == torch.bfloat16 else _lib.ETP_F32)
+        if not self.handle:
+            raise _lib.EtpError("etp_waypoint_create: " + self.L.etp_last_error().decode())
+        info = _lib.ParamInfo()
+        self.table = []
+        for i in range(self.L.etp_waypoint_param_count(self.handle)):
+            check(self.L.etp_waypoint_param_info(self.handle, i, ctypes.byref(info)), "etp_waypoint_param_info")
+            self.table.append((info.name.decode(), tuple(int(info.shape[k]) for k in range(info.ndim)), int(info.offset)))
+        self.total = int(self.L.etp_waypoint_arena_elems(self.handle))
+        self.n_matrix = int(self.L.etp_waypoint_matrix_elems(self.handle))
+        dev = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+        self.arena = torch.zeros(self.total, dtype=torch.float32, device=dev)
+        self.shadow = None
+        self._shadow_version = -1
+        self._ws: Dict[int, torch.Tensor] = {}
+        self._views: List[tuple] = []
+        for name, shape, off in self.table:
+            n = int(np.prod(shape))
+            p = nn.Parameter(self.arena[off:off + n].view(shape), requires_grad=False)
+            mod = self
+            parts = name.split(".")
+            for part in parts[:-1]:
+                if part not in mod._modules:
+                    mod.add_module(part, _Node())
+                mod = mod._modules[part]
+            mod.register_parameter(parts[-1], p)
+            self._views.append((p, off, n, shape))
+        self._bind()
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.L.etp_waypoint_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def _bind(self):
+        if self.arena.device.type != "cuda":
+            return
+        if self.compute_dtype == torch.bfloat16:
+            self.shadow = torch.zeros(self.n_matrix, dtype=torch.bfloat16, device=self.arena.device)
+        check(self.L.etp_waypoint_bind(self.handle, ptr(self.arena), ptr(self.shadow)), "etp_waypoint_bind")
+        self._shadow_version = -1
+
+    def _apply(self, fn, recurse=True):
+        new = fn(self.arena)
+        if new.dtype != torch.float32:
+            raise TypeError("the predictor's master parameters stay fp32; choose the compute dtype at construction")
+        if new.device != self.arena.device:
+            with torch.no_grad():
+                self.arena = new.contiguous()
+                for p, off, n, shape in self._views:
+                    p.data = self.arena[off:off + n].view(shape)
+                self._ws.clear()
+                self._bind()
+        return self
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        r = super().load_state_dict(state_dict, strict=strict, assign=False)
+        self._shadow_version = -1
+        return r
+
+    def _version(self) -> int:
+        return self.arena._version + sum(p._version for p, _, _, _ in self._views)
+
+    def forward(self, rgb_feats, depth_feats) -> torch.Tensor:
+        """TRM_net.py:62-88.  depth_feats [12*B,128,4,4] (or [12*B,2048]); rgb_feats is ignored, as in the reference (only its
+        batch size was read there).  -> logits [B,120,12] fp32, the angle axis already rolled by HEATMAP_OFFSET."""
+        _require_gpu(self.arena, "BinaryDistPredictorTRM")
+        x = depth_feats.reshape(depth_feats.shape[0], -1).to(device=self.arena.device, dtype=torch.float32).contiguous()
+        assert x.shape[1] == 2048 and x.shape[0] % NUM_IMGS == 0, tuple(x.shape)
+        B = x.shape[0] // NUM_IMGS
+        if self.shadow is not None and self._version() != self._shadow_version:
+            check(self.L.etp_waypoint_refresh_weights(self.handle, _stream()), "etp_waypoint_refresh_weights")
+            self._shadow_version = self._version()
+        ws = self._ws.get(B)
+        if ws is None:
+            ws = torch.empty(int(self.L.etp_waypoint_ws_bytes(self.handle, B)), dtype=torch.uint8, device=self.arena.device)
+            self._ws[B] = ws
+        logits = torch.empty(B, NUM_ANGLES, NUM_CLASSES, dtype=torch.float32, device=self.arena.device)
+        check(self.L.etp_waypoint_fwd(self.handle, ptr(x), B, ptr(logits), ptr(ws), _stream()), "etp_waypoint_fwd")
+        return logits
+
+    def candidates(self, logits: torch.Tensor, in_train: bool, generator: Optional[torch.Generator] = None,
+                   uniforms: Optional[torch.Tensor] = None) -> CandidateTable:
+        """Policy_ViewSelection_ETP.py:220-282 on the device.  in_train draws one uniform per candidate slot with torch.rand on the
+        device (`generator`), or takes `uniforms` [B,5]; torch's Categorical stream is not reproduced."""
+        if in_train and uniforms is None:
+            uniforms = torch.rand(logits.shape[0], MAX_PREDICTIONS, device=logits.device, generator=generator)
+        return waypoint_tail(logits, MAX_PREDICTIONS, NMS_SIGMA, uniforms if in_train else None)
+
+
+# ---- ETP.forward(mode='waypoint') -----------------------------------------------------------------------------------------------
+def angle_feature_torch(headings: torch.Tensor) -> torch.Tensor:
+    """vlnce_baselines/models/utils.py:49-57"""
+    z = torch.zeros_like(headings)
+    return torch.stack([torch.sin(headings), torch.cos(headings), torch.sin(z), torch.cos(z)]).float().T
+
+
+def pano_constants():
+    """Policy_ViewSelection_ETP.py:141-143"""
+    idx = np.arange(0, 12, dtype=np.int64)
+    return idx, angle_feature_torch(torch.from_numpy((1 - idx / 12) * 2 * math.pi))
+
+
+def waypoint_mode(net, waypoint_predictor, observations, in_train: bool, generator=None, uniforms=None):
+    """Policy_ViewSelection_ETP.py:172-342 with the predictor and the heat-map tail on the device and ONE device-to-host copy (the
+    candidate table) in place of the per-episode .nonzero() / .cpu() / .tolist() calls.  `net` supplies depth_encoder,
+    rgb_encoder, space_pool_rgb, space_pool_depth, pano_angle_fts and pano_img_idxes."""
+    batch_size = observations["rgb"].shape[0]
+    depth_batch = torch.zeros_like(observations["depth"]).repeat(NUM_IMGS, 1, 1, 1)
+    rgb_batch = torch.zeros_like(observations["rgb"]).repeat(NUM_IMGS, 1, 1, 1)
+    # reverse the order of the input images to clockwise (:182-190): view a_count of every episode goes to slot (12 - a_count) % 12
+    a_count = 0
+    for k, v in observations.items():
+        if "depth" in k:
+            ra_count = (NUM_IMGS - a_count) % NUM_IMGS
+            depth_batch[ra_count::NUM_IMGS] = v
+            rgb_batch[ra_count::NUM_IMGS] = observations[k.replace("depth", "rgb")]
+            a_count += 1
+    obs_view12 = {"depth": depth_batch, "rgb": rgb_batch}
+    depth_embedding = net.depth_encoder(obs_view12)       # [12B, 128, 4, 4]
+    rgb_embedding = net.rgb_encoder(obs_view12)           # [12B, 512]
+
+    logits = waypoint_predictor(rgb_embedding, depth_embedding)
+    cand = waypoint_predictor.candidates(logits, in_train, generator=generator, uniforms=uniforms)
+    host = cand.table.cpu().numpy()                       # the one device-to-host copy of the call
+
+    # back to counter-clockwise (:201-213) and the two average pools (:289-290)
+    rgb_r = rgb_embedding.reshape(batch_size, NUM_IMGS, 512, 1, 1)
+    dep_r = depth_embedding.reshape(batch_size, NUM_IMGS, 128, 4, 4)
+    rgb_feats = net.space_pool_rgb(torch.cat((rgb_r[:, 0:1, :], torch.flip(rgb_r[:, 1:, :], [1])), dim=1))
+    depth_feats = net.space_pool_depth(torch.cat((dep_r[:, 0:1, :], torch.flip(dep_r[:, 1:, :], [1])), dim=1))
+
+    cand_rgb, cand_depth, cand_angle_fts, cand_img_idxes, cand_angles, cand_distances = [], [], [], [], [], []
+    for j in range(batch_size):
+        n = int(host[0, j, 0])
+        angle_idxes = torch.from_numpy(host[5 if in_train else 1, j, :n].astype(np.int64))
+        distance_idxes = torch.from_numpy(host[6 if in_train else 2, j, :n].astype(np.int64))
+        angle_rad_c = angle_idxes.float() / 120 * 2 * math.pi                   # clockwise (:307)
+        angle_rad_cc = 2 * math.pi - angle_idxes.float() / 120 * 2 * math.pi    # counter-clockwise (:308)
+        cand_angle_fts.append(angle_feature_torch(angle_rad_c))
+        cand_angles.append(angle_rad_cc.tolist())
+        cand_distances.append(((distance_idxes + 1) * 0.25).tolist())
+        img_idxes = 12 - (angle_idxes.numpy() + 5) // 10                        # counter-clockwise (:313-314)
+        img_idxes[img_idxes == 12] = 0
+        cand_img_idxes.append(img_idxes)
+        cand_rgb.append(rgb_feats[j, img_idxes, ...])
+        cand_depth.append(depth_feats[j, img_idxes, ...])
+    return {
+        "cand_rgb": cand_rgb, "cand_depth": cand_depth, "cand_angle_fts": cand_angle_fts, "cand_img_idxes": cand_img_idxes,
+        "cand_angles": cand_angles, "cand_distances": cand_distances,
+        "pano_rgb": rgb_feats, "pano_depth": depth_feats,
+        "pano_angle_fts": deepcopy(net.pano_angle_fts), "pano_img_idxes": deepcopy(net.pano_img_idxes),
+    }

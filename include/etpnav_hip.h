@@ -214,6 +214,44 @@ int etp_attn_bwd_kv(const etp_attn_bwd_desc* d, int kv_mod, int sum_steps, etp_s
  * etp_gemm + etp_attn_bwd.  Results equal that pair's (the tile is rounded to bf16 exactly where the GEMM stored it). */
 int etp_attn_bwd_proj(const etp_attn_bwd_desc* d, const void* w_out, int64_t ldw, etp_stream_t stream);
 
+/* Neighbourhood attention of the waypoint predictor (vlnce_baselines/waypoint_pred/transformer/waypoint_bert.py:49-90 under the mask
+ * of waypoint_pred/utils.py:90-102, TRM_net.py:51-53,74-77), forward only -- the predictor is frozen and in eval()
+ * (ss_trainer_ETP.py:201-202), so there is no dropout and nothing is saved for a backward:
+ *   ctx[b*12 + i, h*64 : h*64+64] = sum_{o = -neighbor .. neighbor} softmax_o(alpha q_i . k_{(i+o) mod 12}) v_{(i+o) mod 12}
+ * Q, K, V: head-interleaved rows [B*12, ld] in `dtype` (12 heads of 64 at column h*64; three slices of one [B*12, 2304] product
+ * or separate buffers), ctx [B*12, ldc] in `dtype`.  Twelve tokens, twelve heads, head dimension 64 are fixed.  The reference adds
+ * -10000 to the scores outside the window, which in fp32 equals leaving those keys out (exp(-10000 + d) == 0): they are not read.
+ * fp32 scores, probabilities and accumulation whatever `dtype` is; ctx is rounded once, at its store.  Columns 768 .. ldc-1 of ctx are
+ * left alone.
+ * ETP_ERR_INVALID before anything is launched: neighbor outside 0 .. 5 (utils.py:91), B <= 0, an operand not aligned to four elements
+ * (8 bytes bf16, 16 bytes fp32), a leading dimension below 768 or not a multiple of 4. */
+int etp_ring_attn_fwd(int dtype, const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* ctx,
+                      int64_t ldc, int B, int neighbor, float alpha, etp_stream_t stream);
+
+/* From heat-map logits to waypoint candidates, one workgroup per episode (vlnce_baselines/models/Policy_ViewSelection_ETP.py:220-239,
+ * 247-282, 304-305, 313-314; waypoint_pred/utils.py:8-64).  logits [B,120,12] fp32 (angle x distance, already rolled by
+ * HEATMAP_OFFSET, TRM_net.py:84-86):
+ *   heat [B,120,12]      softmax over the 1 440 cells
+ *   nms_map [B,120,12]   nms(wrap(heat), max_predictions = max_pred, sigma = (sigma_x, sigma_y)) without the two wrap rows.  The wrapped
+ *                        map has 122 angle rows (row 0 = angle 119, row 121 = angle 0).  Each round takes the arg-max (lowest flat index
+ *                        among equal values), records it and zeroes the cells with min(|x - x_mu|, |x - x_mu + 12|) <= sigma_x and
+ *                        |y - y_mu| <= sigma_y, where x_mu = ix % 12 and y_mu = ix / 12 is a TRUE division (utils.py:55): the centre on
+ *                        the angle axis is fractional.  A pick in a wrap row is lost with the row.
+ *   cand_count [B]       int32, number of non-zero cells of nms_map (<= max_pred)
+ *   cand_angle, cand_dist, cand_img_cw, cand_img_ccw [B,max_pred]   int32, the non-zero cells in row-major order: angle index, distance
+ *                        index, ((angle+5)/10) % 12 (:263-264) and (12 - (angle+5)/10) % 12 (:313-314); -1 beyond the count
+ * uniforms [B,max_pred] fp32 in [0,1) or NULL.  Non-NULL (in_train, :247-282): per candidate, the softmax over the 10 x 12 logits of its
+ *   image sector (taken from the logits rolled back by 5) and one inverse-CDF draw -- the first index whose inclusive prefix sum, added
+ *   serially in index order, exceeds u * total -- in place of torch.distributions.Categorical.sample (whose stream is not reproduced):
+ *   samp_angle = act / 12 + pointer, samp_dist = act % 12, pointer = (sector-1)*10 + 5, or 0 for sector 0 (:275-280); -1 beyond the count.
+ *   With uniforms NULL samp_angle / samp_dist may be NULL and are not written.
+ * Plain stores only, no atomics: a second run returns the same bits.
+ * ETP_ERR_INVALID before anything is launched: max_pred outside 1 .. 8, B <= 0, logits / heat / nms_map not 16-byte aligned, a table
+ * not 4-byte aligned, uniforms without samp_angle / samp_dist. */
+int etp_waypoint_tail(const float* logits, int B, int max_pred, float sigma_x, float sigma_y, const float* uniforms, float* heat,
+                      float* nms_map, int32_t* cand_count, int32_t* cand_angle, int32_t* cand_dist, int32_t* cand_img_cw,
+                      int32_t* cand_img_ccw, int32_t* samp_angle, int32_t* samp_dist, etp_stream_t stream);
+
 /* Residual-stream convention: tensors that flow from one LayerNorm / residual add to the next are ALWAYS fp32 (as under
  * the reference's autocast, where LayerNorm and residual adds stay fp32); `*_lp` arguments are optional copies in the GEMM
  * operand dtype `dtype` for the next MFMA product (pass NULL in fp32 mode). */
@@ -427,6 +465,35 @@ int etp_planner_refresh_part(etp_planner* p, int part, etp_stream_t stream);
 /* bf16 shadow of the text encoder, layer 0 on `main` and layers >= 1 on `side`; the next etp_txt_fwd issued on `main` waits for
  * the side cast after its layer 0 (takes ~40 us of weight casting off the head of the dependent chain of a training step). */
 int etp_planner_refresh_text_split(etp_planner* p, etp_stream_t main, etp_stream_t side);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Waypoint predictor engine: BinaryDistPredictor_TRM.forward (vlnce_baselines/waypoint_pred/TRM_net.py:62-88, called first in
+ * every rollout step, ss_trainer_ETP.py:825-830 -> Policy_ViewSelection_ETP.py:198-199) over one flat parameter arena.  Forward
+ * only: the predictor is frozen and in eval() (ss_trainer_ETP.py:201-202,490,586,711).
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct etp_waypoint etp_waypoint;
+etp_waypoint* etp_waypoint_create(int dtype);                /* ETP_F32 | ETP_BF16; NULL on error */
+void etp_waypoint_destroy(etp_waypoint* w);
+/* The parameter table: names are the keys of the reference module's state dict in its order (TRM_net.py:27-60), the two modules
+ * the forward never uses (visual_merge, mergefeats_LayerNorm) included, so that a strict load sees every key.  offset: element
+ * offset in the fp32 arena; the GEMM matrices lead it ([0, etp_waypoint_matrix_elems)) and have a bf16 shadow at the same offsets. */
+int etp_waypoint_param_count(const etp_waypoint* w);
+int etp_waypoint_param_info(const etp_waypoint* w, int i, etp_param_info* out);
+int64_t etp_waypoint_arena_elems(const etp_waypoint* w);
+int64_t etp_waypoint_matrix_elems(const etp_waypoint* w);
+/* params: fp32 arena; shadow: bf16 copy of the matrix region (NULL in fp32 mode).  Both 256-byte aligned. */
+int etp_waypoint_bind(etp_waypoint* w, float* params, void* shadow);
+/* bf16 mode: shadow = bf16(params) over the matrix region (once after loading the checkpoint: the weights are frozen). */
+int etp_waypoint_refresh_weights(etp_waypoint* w, etp_stream_t stream);
+/* logits [B,120,12] fp32 (angle x distance, already rolled by HEATMAP_OFFSET = 5, TRM_net.py:83-86) from the depth encoder's
+ * embeddings depth_feats [12*B, 2048] fp32 (nn.Flatten of [12*B,128,4,4], views of an episode in clockwise order; the rgb_feats
+ * argument of the reference is ignored by it, TRM_net.py:65-72).  x = relu(fc(depth)); two post-LN BERT layers whose tokens attend
+ * to their ring neighbours (etp_ring_attn_fwd, neighbor = TRM_NEIGHBOR = 1) with Q, K, V from one N = 2304 product; the two-layer
+ * classifier; the roll.  Residual stream and LayerNorms fp32 in both modes; `dtype` selects the GEMM / attention operand precision.
+ * ws: etp_waypoint_ws_bytes(w, B) bytes of caller-owned scratch, 256-byte aligned (one plan for the whole call).  18 launches in
+ * fp32 mode, 20 in bf16 mode, whatever B is. */
+int64_t etp_waypoint_ws_bytes(const etp_waypoint* w, int B);
+int etp_waypoint_fwd(etp_waypoint* w, const float* depth_feats, int B, float* logits, void* ws, etp_stream_t stream);
 
 /* Activations that cross these entry points (txt_embeds, pano_embeds, gmap_img_fts, gmap_embeds and their gradients) are
  * fp32 in BOTH modes, as they are under the reference's autocast (outputs of fp32 LayerNorms); `dtype` only selects the
