@@ -251,7 +251,7 @@ class profiled:
 
 def force_gemm_tile(tile: str = "") -> None:
     """Tuning aid: force a tile class of gemm.hip's kernels for the following launches ("" / "auto" = the library's own choice).
-    The mm32 family is consulted BEFORE gemm.hip's tile choice (csrc/gemm_mm32.hip::mm32_class), so forcing a gemm.hip class
+    The selection (csrc/gemm.hip::gemm_select) tries the mm32 family BEFORE gemm.hip's tile classes, so forcing a gemm.hip class
     also switches mm32 off -- otherwise an eligible bf16 product would silently keep running the mm32 kernel."""
     tile = "" if tile == "auto" else tile
     set_option("GEMM_TILE", tile)

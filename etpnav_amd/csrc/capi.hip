@@ -224,16 +224,27 @@ int etp_gemm(const etp_gemm_desc* d, etp_stream_t stream) {
   ETP_TRY(desc_to_args(d, g));
   return launch_gemm(d->dtype, d->c_dtype, d->trans_a, d->trans_b, g, d->batch > 0 ? d->batch : 1, (hipStream_t)stream);
 }
-int etp_gemm_group(const etp_gemm_desc* d, int n, etp_stream_t stream) {
-  ETP_REQUIRE(d && n >= 1 && n <= ETP_GEMM_GROUP_MAX, "1..8 descriptors");
-  GemmArgs gs[ETP_GEMM_GROUP_MAX];
+// descriptors of a group -> gs, with etp_gemm_group's checks (shared with etp_gemm_instance: the same refusals, word for word)
+static int group_to_args(const etp_gemm_desc* d, int n, GemmArgs* gs) {
+  if (!(d && n >= 1 && n <= ETP_GEMM_GROUP_MAX)) return fail(ETP_ERR_INVALID, "etp_gemm_group: 1..8 descriptors");
   for (int i = 0; i < n; ++i) {
     ETP_TRY(desc_to_args(d + i, gs[i]));
-    ETP_REQUIRE(d[i].dtype == d[0].dtype && d[i].c_dtype == d[0].c_dtype && d[i].trans_a == d[0].trans_a &&
-                    d[i].trans_b == d[0].trans_b && d[i].batch <= 1 && d[i].ksplit <= 1,
-                "grouped products share dtype / storage class and are unbatched, unsplit");
+    if (!(d[i].dtype == d[0].dtype && d[i].c_dtype == d[0].c_dtype && d[i].trans_a == d[0].trans_a && d[i].trans_b == d[0].trans_b &&
+          d[i].batch <= 1 && d[i].ksplit <= 1))
+      return fail(ETP_ERR_INVALID, "etp_gemm_group: grouped products share dtype / storage class and are unbatched, unsplit");
   }
+  return ETP_OK;
+}
+int etp_gemm_group(const etp_gemm_desc* d, int n, etp_stream_t stream) {
+  GemmArgs gs[ETP_GEMM_GROUP_MAX];
+  ETP_TRY(group_to_args(d, n, gs));
   return launch_gemm_group(d[0].dtype, d[0].c_dtype, d[0].trans_a, d[0].trans_b, gs, n, (hipStream_t)stream);
+}
+int etp_gemm_instance(const etp_gemm_desc* d, int n, char* out, int cap) {
+  GemmArgs gs[ETP_GEMM_GROUP_MAX];
+  if (n == 1) ETP_TRY(desc_to_args(d, gs[0]));
+  else ETP_TRY(group_to_args(d, n, gs));
+  return gemm_instance_query(d[0].dtype, d[0].c_dtype, d[0].trans_a, d[0].trans_b, gs, n, n == 1 && d->batch > 0 ? d->batch : 1, out, cap);
 }
 
 int etp_colsum(int dtype, const void* dy, int64_t ld, float* db, int M, int N, etp_stream_t s) {

@@ -215,6 +215,9 @@ constexpr int ETP_GEMM_GROUP_MAX = 8;
 struct GemmGroup { int n; int xcd_chunks; int tile_start[ETP_GEMM_GROUP_MAX + 1]; GemmArgs g[ETP_GEMM_GROUP_MAX]; };
 int launch_gemm_group(int dtype, int c_dtype, int transA, int transB, const GemmArgs* gs, int n, hipStream_t st);
 bool gemm_uses_dma(int dtype, int K, int ksplit);   // true when launch_gemm will take the LDS-DMA kernel for this reduction
+// host only: name of the kernel instance launch_gemm (n == 1) / launch_gemm_group (2 <= n <= ETP_GEMM_GROUP_MAX) would run -> its
+// length (written to out, truncated to cap), or the refusal the launch itself would return
+int gemm_instance_query(int dtype, int c_dtype, int transA, int transB, const GemmArgs* gs, int n, int nbatch, char* out, int cap);
 // graphrec.hip: explicit hipGraph recording of everything issued through launch.h
 int rec_begin();
 int rec_end(hipGraph_t* graph, hipGraphExec_t* exec, long* n_kernels, long* n_edges);

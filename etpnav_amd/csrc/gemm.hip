@@ -433,140 +433,264 @@ unsigned long long* probe_slot(const char* name, long wgs, int M, int N, int K) 
   return p;
 }
 
-template <typename T, typename TC, bool TA, bool TB, int BM, int BN, int STAGES /*0 = register-staged kernel*/>
-static int launch_one(const GemmArgs& g_in, int nbatch, hipStream_t st) {
-  constexpr int PAD = STAGES == 0 ? 32 : 0;
-  using GA = TileGeom<T, TA, BM, PAD>;
-  using GB = TileGeom<T, TB, BN, PAD>;
-  constexpr int smem_loop = (STAGES == 0 ? 2 : STAGES) * (GA::BYTES + GB::BYTES), smem_c = BM * (BN + 4) * 4;
-  constexpr int smem = smem_loop > smem_c ? smem_loop : smem_c;
-  void (*kern)(const GemmArgs);
-  if constexpr (STAGES == 0) kern = gemm_kernel<T, TC, TA, TB, BM, BN>;
-  else kern = gemm_dma_kernel<T, TC, TA, TB, BM, BN, STAGES>;
-  ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(kern), smem));
-  const int tiles = ((g_in.M + BM - 1) / BM) * ((g_in.N + BN - 1) / BN);
-  dim3 grid(tiles, nbatch * g_in.ksplit, 1);
-  GemmArgs g = g_in;
-  char nm[96];
-  snprintf(nm, sizeof(nm), "gemm%s<%s,%s,%s%s,%dx%d,s%d>", STAGES ? "_dma" : "", sizeof(T) == 2 ? "bf16" : "f32",
-           sizeof(TC) == 2 ? "bf16" : "f32", TA ? "T" : "N", TB ? "N" : "T", BM, BN, STAGES);   // BLAS-style opA,opB
-  g.dbg = (STAGES > 0 && g_probe_buf) ? probe_slot(nm, (long)tiles * nbatch * g_in.ksplit, g.M, g.N, g.K) : nullptr;
-  ProfRec rec;
-  const bool prof = g_prof_on && !rec_active() && prof_wanted(nm);
-  if (prof) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    rec.id = prof_id(nm);
-    rec.flops = 2.0 * g.M * g.N * g.K * nbatch;
-    rec.bytes = ((double)g.M * g.K + (double)g.N * g.K) * nbatch * sizeof(T) + (double)g.M * g.N * nbatch * sizeof(TC);
-    ETP_CHECK_HIP(hipEventCreate(&rec.a));
-    ETP_CHECK_HIP(hipEventCreate(&rec.b));
-    ETP_CHECK_HIP(hipEventRecord(rec.a, st));
-  }
-  ETP_LAUNCH(kern, grid, dim3(STAGES == 0 ? 256 : 64 * TileWaves<BM, BN>::NW), smem, st, g);
-  ETP_CHECK_LAUNCH("gemm");
-  if (prof) {
-    ETP_CHECK_HIP(hipEventRecord(rec.b, st));
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof_recs.push_back(rec);
-  }
-  return ETP_OK;
+// ---- instance selection: pure host arithmetic on prepared arguments and the switches -- no HIP call, nothing launched ---------------
+// A forced tile switch (GEMM_TILE, GROUP_TILE), read here and nowhere else: class letter ('3' = "32", '6' = "64", '1' = "128",
+// 'w', '2' = "256"; 0 = not forced), ring depth ("s2" .. "s4"; 0 = the class's own) and "r" = register-staged kernels only.
+struct TileForce { char cls; int stages; bool reg; };
+static TileForce tile_force(Opt o) {
+  const char* f = opt_str(o);
+  TileForce t{0, 0, false};
+  if (!f || !f[0]) return t;
+  t.cls = f[0];
+  if (strstr(f, "s2")) t.stages = 2;
+  if (strstr(f, "s3")) t.stages = 3;
+  if (strstr(f, "s4")) t.stages = 4;
+  t.reg = strchr(f, 'r') != nullptr;
+  return t;
 }
-
-static bool dma_ok(int bk, int K, int ksplit) {
+static bool dma_ok(int bk, int K, int ksplit, const TileForce& f) {
   // LDS-DMA main loop needs whole 128-byte slabs in every split of the reduction
   bool dma = (K % bk == 0) && (K >= 2 * bk);
   if (ksplit > 1) dma = dma && (K % ksplit == 0) && ((K / ksplit) % bk == 0);
-  const char* force = opt_str(OPT_GEMM_TILE);
-  if (force && strchr(force, 'r')) dma = false;
-  return dma;
+  return dma && !f.reg;
 }
-bool gemm_uses_dma(int dtype, int K, int ksplit) { return dma_ok(dtype == ETP_BF16 ? 64 : 32, K, ksplit); }
+bool gemm_uses_dma(int dtype, int K, int ksplit) { return dma_ok(dtype == ETP_BF16 ? 64 : 32, K, ksplit, tile_force(OPT_GEMM_TILE)); }
 
-template <typename T, typename TC, bool TA, bool TB>
-static int launch_tiles(const GemmArgs& g, int nbatch, hipStream_t st) {
-  // Tile choice (round 3, after the pipelined main loop; sweep: tools/gemm_sweep.py -> profiles/r03_gemm_sweep.json).
+// shapes the mm32 family (gemm_mm32.hip) takes: whole tiles only
+static bool mm32_ok(const GemmArgs& g, int bm, int bn) {
+  return g.M % bm == 0 && g.N % bn == 0 && g.K % 64 == 0 && g.K >= 128 && g.ksplit == 1 && g.vec_epilogue && g.out_mode != 2 &&
+         g.lda % 8 == 0 && g.ldb % 8 == 0;
+}
+static long tiles_up(const GemmArgs& g, int bm, int bn) { return (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn); }
+static long tiles_whole(const GemmArgs& g, int bm, int bn) { return (long)(g.M / bm) * (g.N / bn); }
+
+// The instance launch_gemm runs for the PREPARED arguments `g` (prepare_args); (ta, tb) is one of NT, NN, TN.
+GemmInstance gemm_select(int dtype, int c_dtype, int ta, int tb, const GemmArgs& g, int nbatch) {
+  const bool bf16 = dtype != ETP_F32;
+  GemmInstance r{GEMM_REG, false, bf16, bf16 && c_dtype != ETP_F32, ta != 0, tb != 0, 64, 64, 0, 1};
+  auto pick = [&r](int family, int bm, int bn, int stages, int ks = 1) {
+    r.family = family; r.BM = bm; r.BN = bn; r.stages = stages; r.ks = ks;
+    return r;
+  };
+  // -- whole-tile bf16 products: the 32x32x16 family comes first.  MM32=0 switches it off (A/B runs against gemm.hip's kernels),
+  // MM32=128 / 64 / 264 / 262 forces that class for every eligible product whatever the tile count (tests).
+  const int mm32 = opt_int(OPT_MM32, 1);
+  if (dtype == ETP_BF16 && mm32 && nbatch == 1) {
+    const bool ok128 = mm32_ok(g, 128, 128), ok64 = mm32_ok(g, 128, 64), ok_k2 = ok64 && g.K % 128 == 0 && g.K >= 256;
+    const long tw = tiles_whole(g, 128, 64);
+    int cls = 0;                                      // 128: 128x128 ring 2 | 64: 128x64 ring 3 | 264 / 262: 128x64 split reduction
+    if (mm32 == 128) cls = ok128 ? 128 : 0;
+    else if (mm32 == 64) cls = ok64 ? 64 : 0;
+    else if (mm32 == 264 || mm32 == 262) cls = ok_k2 ? mm32 : (ok64 ? 64 : 0);
+    else if (ok128 && tiles_whole(g, 128, 128) >= 320) cls = 128;
+    else if (ok64 && tw >= 200) {
+      // 128x64: the N = 768 products of the M = B*L rows (240 workgroups) and everything between them and the 128x128 class.
+      // One workgroup per CU in ONE resident round (200 .. 256 tiles): the split-reduction form (mm32::tile, KS = 2) puts a second
+      // wavefront on every SIMD.  Measured (profiles/r06_k2_bench.txt, r06_ab_runs.json): isolated launches 3 - 6 % faster with two rings
+      // of three (2560x768x3072: 18.5 -> 17.5 us), 20 % SLOWER with two rings of two, and the step +0.3 % with it (4.054 / 4.056 against
+      // 4.043 / 4.038 ms): these loops move 283 MB through the CUs in 13.3 us = 21 TB/s, the rate the feed bench reaches with nothing but
+      // the loads (profiles/r04a_feed_bench.txt) -- they are at the L2 -> CU feed, not waiting on latency, and a 144-KB workgroup displaces
+      // the leaf workgroup that shared its CU.  So: OFF by default; MM32_K2 = 264 / 262 turns the class on.
+      const int k2 = opt_int(OPT_MM32_K2, 0);
+      cls = (k2 && tw <= 256 && ok_k2) ? (k2 == 262 ? 262 : 264) : 64;
+    }
+    if (cls >= 262 && ta) cls = 64;                   // the split-reduction tile exists for a row-major A only: TN keeps the 64 class
+    if (cls == 128) return pick(GEMM_MM32, 128, 128, 2);
+    if (cls == 264) return pick(GEMM_MM32, 128, 64, 3, 2);     // two rings of three (144 KB)
+    if (cls == 262) return pick(GEMM_MM32, 128, 64, 2, 2);     // two rings of two (96 KB: a 64-KB leaf workgroup fits beside it)
+    if (cls == 64) return pick(GEMM_MM32, 128, 64, 3);
+  }
+  // -- gemm.hip's tile classes (round 3, after the pipelined main loop; sweep: tools/gemm_sweep.py -> profiles/r03_gemm_sweep.json).
   // What bounds a tile class on this chip is the L2 -> LDS feed (~64 B/clk/CU): per 128-byte slab a 64x64 tile moves
   // 16 KiB for 8 MFMAs per wave, 128x64 24 KiB for 16, 128x128 32 KiB for 32.  So: the largest tile that still gives
   // (nearly) every CU a workgroup.
   //   128x128 (ring 2, two workgroups per CU)   when it yields >= ~1.4 workgroups per CU,
   //   128x64  (ring 4, one workgroup per CU)    when it yields >= ~0.8 per CU (the M = 2560, N = 768 products: 240),
   //   64x64   (ring 3; ring 4 below one workgroup per CU) otherwise.
-  constexpr int BK = MmaTraits<T>::BK;
-  const long t128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * nbatch * g.ksplit;
-  const long tw = (long)((g.M + 127) / 128) * ((g.N + 63) / 64) * nbatch * g.ksplit;
-  const long t64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64) * nbatch * g.ksplit;
+  const int BK = bf16 ? 64 : 32;
+  const long per = (long)nbatch * g.ksplit;
+  const long t128 = tiles_up(g, 128, 128) * per, tw = tiles_up(g, 128, 64) * per, t64 = tiles_up(g, 64, 64) * per;
   // 256x128 (eight wavefronts, one workgroup per CU) exists as a FORCED tile class only ("256s2" / "256s3"): measured on
   // MI355X (profiles/r03d_*, r03_ab_runs.json group c5) its loop runs at the same rate per CU as two co-resident 128x128
   // workgroups (1.0 us per 256x128x64 slab of work either way, ~50 % MFMA issue rate at two wavefronts per SIMD) while its
   // 180 / 216 / 240 tiles leave 6-30 % of the CUs idle: step 4.51 ms with it against 4.37 ms; no shape up to 8192 rows wins.
   bool huge = false;
-  bool big = !huge && (g.M >= 128 && g.N >= 128 && t128 >= 360);
-  bool wide = !huge && !big && g.M >= 128 && g.N >= 64 && tw >= 200 && tw <= 520 && nbatch == 1;
+  bool big = g.M >= 128 && g.N >= 128 && t128 >= 360;
   // The 128x64 class is OFF by default: alone it is the faster kernel for the M = 2560, N = 768 products (25.1 vs 28.4 us at
   // K = 3072 in a single-stream step), but in the real three-stream step the 64x64 class wins, 4.30 vs 4.35 ms per step in
   // three same-box A/B pairs (profiles/r03_ab_runs.json groups c1, c8): its 48-KiB, ~130-register workgroups pack beside the
-  // leaf kernels' workgroups where one 96-KiB 128x64 workgroup per CU does not.  ETP_GEMM_WIDE=1 enables it.
-  const bool wide_on = opt_int(OPT_GEMM_WIDE, 0) == 1;
-  if (!wide_on) wide = false;
-  const bool dma = dma_ok(BK, g.K, g.ksplit);
-  int stages = (big || huge) ? 2 : (wide ? 4 : 3);
-  if (!huge && !big && !wide && t64 <= 320 && g.K >= 4 * BK) stages = 4;
-  const char* force = opt_str(OPT_GEMM_TILE);   // tuning aid (tools/gemm_sweep.py): "128", "64", "w" + optional "s2".."s4", "64r"
-  if (force && force[0]) {
-    huge = force[0] == '2';                        // "256", "256s3"
-    if (force[0] == '1' || force[0] == '6') { big = force[0] == '1'; wide = false; }
-    if (force[0] == 'w') { wide = true; big = false; }
+  // leaf kernels' workgroups where one 96-KiB 128x64 workgroup per CU does not.  GEMM_WIDE=1 enables it.
+  bool wide = !big && opt_int(OPT_GEMM_WIDE, 0) == 1 && g.M >= 128 && g.N >= 64 && tw >= 200 && tw <= 520 && nbatch == 1;
+  int stages = big ? 2 : wide ? 4 : (t64 <= 320 && g.K >= 4 * BK) ? 4 : 3;
+  const TileForce f = tile_force(OPT_GEMM_TILE);     // tuning aid (tools/gemm_sweep.py)
+  if (f.cls) {                                       // ("32" leaves big / wide as they were: it only decides the 32x64 rule below)
+    huge = f.cls == '2';
+    if (f.cls == '1' || f.cls == '6') { big = f.cls == '1'; wide = false; }
+    if (f.cls == 'w') { wide = true; big = false; }
     if (huge) { big = false; wide = false; }
-    stages = (big || huge) ? 2 : (wide ? 4 : 3);
-    if (strstr(force, "s2")) stages = 2;
-    if (strstr(force, "s3")) stages = 3;
-    if (strstr(force, "s4")) stages = 4;
+    stages = f.stages ? f.stages : (big || huge) ? 2 : wide ? 4 : 3;
   }
-  if (!dma) {
-    if (big || huge) return launch_one<T, TC, TA, TB, 128, 128, 0>(g, nbatch, st);
-    return launch_one<T, TC, TA, TB, 64, 64, 0>(g, nbatch, st);
-  }
-  if constexpr (sizeof(T) == 2 && !TA) {
+  if (!dma_ok(BK, g.K, g.ksplit, f)) return pick(GEMM_REG, (big || huge) ? 128 : 64, (big || huge) ? 128 : 64, 0);
+  if (bf16 && !ta) {
     // 32x64 tiles (four wavefronts of 16x32, ring 4) for grids that would give fewer than half the CUs a 64x64 workgroup -- the
     // M = 512 node-side products of the x-layers (96 -> 192 workgroups) and everything of config 5.  A lone workgroup's slab
     // time is set by its own wait -> barrier -> read -> MFMA chain (0.24 us per 64x64x64 slab whatever the ring depth or the
     // wavefront count, profiles/r04_gemm_phases.txt), not by bytes: halving the tile rows doubles the workgroups that share
     // the reduction's work at (nearly) the same time per slab.  A row-major only (its 32-row slab is four 1-KiB DMA pieces).
-    // ETP_GEMM_SMALL=0 switches the class off (A/B runs), ETP_GEMM_TILE=32 forces it.
-    const bool small_on = opt_on(OPT_GEMM_SMALL, true);
-    const bool forced = force && force[0];
-    const bool take = forced ? force[0] == '3' : (small_on && nbatch == 1 && g.ksplit == 1 && t64 <= 128 && g.M >= 32 && g.K >= 4 * BK);
-    if (take) return launch_one<T, TC, TA, TB, 32, 64, 4>(g, nbatch, st);
+    // GEMM_SMALL=0 switches the class off (A/B runs), GEMM_TILE=32 forces it.
+    const bool take = f.cls ? f.cls == '3'
+                            : (opt_on(OPT_GEMM_SMALL, true) && nbatch == 1 && g.ksplit == 1 && t64 <= 128 && g.M >= 32 && g.K >= 4 * BK);
+    if (take) return pick(GEMM_DMA, 32, 64, 4);
   }
-  if (huge) {
-    if constexpr (sizeof(T) == 2) {                  // bf16 only: the fp32 parity mode keeps the four-wavefront tiles
-      if (stages == 3) return launch_one<T, TC, TA, TB, 256, 128, 3>(g, nbatch, st);
-      return launch_one<T, TC, TA, TB, 256, 128, 2>(g, nbatch, st);
-    } else {
-      if (stages == 3) return launch_one<T, TC, TA, TB, 128, 128, 3>(g, nbatch, st);
-      return launch_one<T, TC, TA, TB, 128, 128, 2>(g, nbatch, st);
-    }
-  }
-  if (big) {
-    if (stages == 3) return launch_one<T, TC, TA, TB, 128, 128, 3>(g, nbatch, st);
-    return launch_one<T, TC, TA, TB, 128, 128, 2>(g, nbatch, st);
-  }
-  if (wide) {
-    if (stages == 2) return launch_one<T, TC, TA, TB, 128, 64, 2>(g, nbatch, st);
-    if (stages == 3) return launch_one<T, TC, TA, TB, 128, 64, 3>(g, nbatch, st);
-    return launch_one<T, TC, TA, TB, 128, 64, 4>(g, nbatch, st);
-  }
-  if (stages == 4) return launch_one<T, TC, TA, TB, 64, 64, 4>(g, nbatch, st);
-  // (no two-slab ring for 64x64 tiles: its fp32 TN instantiation spilled to scratch, tools/kernel_resources.py; a forced "64s2" runs s3)
-  return launch_one<T, TC, TA, TB, 64, 64, 3>(g, nbatch, st);
+  // Ring depths a class is instantiated with; a forced depth outside them falls back as written here.
+  if (huge && bf16) return pick(GEMM_DMA, 256, 128, stages == 3 ? 3 : 2);
+  if (huge || big) return pick(GEMM_DMA, 128, 128, stages == 3 ? 3 : 2);   // fp32 + "256...": the parity mode keeps the four-wavefront tiles -> 128x128 with the forced ring
+  if (wide) return pick(GEMM_DMA, 128, 64, (stages == 2 || stages == 3) ? stages : 4);
+  return pick(GEMM_DMA, 64, 64, stages == 4 ? 4 : 3);   // no two-slab ring for 64x64 tiles (its fp32 TN instantiation spilled to scratch, tools/kernel_resources.py): a forced "64s2" runs s3
 }
 
+// The instance launch_gemm_group runs for a PREPARED group of n >= 2 problems.
+GemmInstance gemm_group_select(int dtype, int c_dtype, int ta, int tb, const GemmGroup& grp) {
+  const bool bf16 = dtype != ETP_F32;
+  GemmInstance r{GEMM_DMA, true, bf16, bf16 && c_dtype != ETP_F32, ta != 0, tb != 0, 64, 64, 3, 1};
+  auto pick = [&r](int family, int bm, int bn, int stages) {
+    r.family = family; r.BM = bm; r.BN = bn; r.stages = stages;
+    return r;
+  };
+  bool all_big = true, all_huge = bf16, mm_128 = true, mm_256 = true;
+  long t128 = 0, tm128 = 0, tm256 = 0;
+  int kmin = 1 << 30;
+  for (int i = 0; i < grp.n; ++i) {
+    const GemmArgs& g = grp.g[i];
+    all_big = all_big && g.M >= 128 && g.N >= 128;
+    all_huge = all_huge && g.M >= 256 && g.N >= 128;
+    mm_128 = mm_128 && mm32_ok(g, 128, 128);
+    mm_256 = mm_256 && mm32_ok(g, 256, 128);
+    t128 += tiles_up(g, 128, 128); tm128 += tiles_whole(g, 128, 128); tm256 += tiles_whole(g, 256, 128);
+    kmin = g.K < kmin ? g.K : kmin;
+  }
+  // -- mm32: grouped weight gradients (TN, fp32 out) when every problem is whole 128x128 tiles
+  const int mm32 = opt_int(OPT_MM32, 1);
+  if (dtype == ETP_BF16 && c_dtype == ETP_F32 && ta && tb && mm32 && mm_128 && (tm128 >= 100 || mm32 == 128)) {
+    // 256x128 tiles (one workgroup per CU, 128x64 per wavefront) when every problem is whole 256x128 tiles, the reduction is long
+    // enough to pay for a tile that has the CU to itself (no second workgroup covers its fill, its epilogue and -- with one
+    // wavefront per SIMD -- the latency of its ds_read_b64_tr_b16 fragment reads) and the list still covers most of the chip.
+    // Measured (tools/experiments/r04_group_class_probe.py, one text layer's four products, us per launch, 128x128 / 256x128):
+    // 512 tokens 18.1 / 24.6, 1152: 29.0 / 34.4, 2560: 51.4 / 61.8, 8192: 148.8 / 143.5 -- only the 8192-token reductions of
+    // BASELINE config 4 take it.  MM32_GROUP=128 / 256 forces a class (tests, A/B runs); a forced 256 on a group that is not
+    // whole 256x128 tiles runs 128x128.
+    const int force = opt_int(OPT_MM32_GROUP, 0);
+    const bool huge = force != 128 && mm_256 && (force == 256 || (kmin >= 4096 && tm256 >= 160));
+    return huge ? pick(GEMM_MM32, 256, 128, 3) : pick(GEMM_MM32, 128, 128, 2);
+  }
+  // -- gemm.hip: 128x128 tiles halve the L2->LDS bytes per FLOP; they pay once the group still gives most CUs a tile.
+  // 256x128: forced only (see gemm_select).  GROUP_TILE "256..." / "128..." on a group with a member below 256x128 / 128x128 runs 64x64
+  // with the forced ring ("s2" -> s3).
+  bool big = all_big && t128 >= 160, huge = false;
+  int stages = big ? 2 : 3;
+  const TileForce f = tile_force(OPT_GROUP_TILE);
+  if (f.cls) {
+    huge = f.cls == '2' && all_huge;
+    big = f.cls == '1' && all_big;
+    stages = f.stages ? f.stages : (big || huge) ? 2 : 3;
+  }
+  if (huge) return pick(GEMM_DMA, 256, 128, stages == 3 ? 3 : 2);
+  if (big) return pick(GEMM_DMA, 128, 128, stages == 3 ? 3 : 2);
+  return pick(GEMM_DMA, 64, 64, stages == 4 ? 4 : 3);
+}
+
+int gemm_instance_name(const GemmInstance& i, char* out, int cap) {
+  const char* fam = i.family == GEMM_MM32 ? (i.grouped ? "mm32_group" : "mm32")
+                                          : (i.grouped ? "gemm_group" : (i.family == GEMM_DMA ? "gemm_dma" : "gemm"));
+  return snprintf(out, cap, "%s<%s,%s,%s%s,%dx%d,s%d%s>", fam, i.bf16 ? "bf16" : "f32", i.c_bf16 ? "bf16" : "f32", i.ta ? "T" : "N",
+                  i.tb ? "N" : "T", i.BM, i.BN, i.stages, i.ks == 2 ? ",k2" : "");   // BLAS-style opA,opB
+}
+
+// ---- the instance list: every kernel this file instantiates --------------------------------------------------------------------------
+// X(grouped, BM, BN, STAGES), STAGES 0 = the register-staged kernel; each entry for (operands, C) in {bf16/bf16, bf16/f32, f32/f32} and
+// storage in {NT, NN, TN}, except where tile_exists says otherwise.
+#define ETP_GEMM_INSTANCES(X)                                                                              \
+  X(false, 64, 64, 0) X(false, 128, 128, 0)                                                                \
+  X(false, 32, 64, 4)                                                                                      \
+  X(false, 64, 64, 3) X(false, 64, 64, 4)                                                                  \
+  X(false, 128, 64, 2) X(false, 128, 64, 3) X(false, 128, 64, 4)                                           \
+  X(false, 128, 128, 2) X(false, 128, 128, 3)                                                              \
+  X(false, 256, 128, 2) X(false, 256, 128, 3)                                                              \
+  X(true, 64, 64, 3) X(true, 64, 64, 4) X(true, 128, 128, 2) X(true, 128, 128, 3) X(true, 256, 128, 2) X(true, 256, 128, 3)
+// 256x128 is bf16 only (the fp32 parity mode keeps the four-wavefront tiles); 32x64 is bf16 with a row-major A only
+template <typename T, bool TA> constexpr bool tile_exists(int bm) { return (bm != 256 || sizeof(T) == 2) && (bm != 32 || (sizeof(T) == 2 && !TA)); }
+
+template <typename T, typename TC, bool TA, bool TB, int BM, int BN, int STAGES, bool GROUPED>
+static GemmKernel tile_kernel() {
+  constexpr int PAD = STAGES == 0 ? 32 : 0;
+  using GA = TileGeom<T, TA, BM, PAD>;
+  using GB = TileGeom<T, TB, BN, PAD>;
+  constexpr int loop = (STAGES == 0 ? 2 : STAGES) * (GA::BYTES + GB::BYTES), ct = BM * (BN + 4) * 4;
+  GemmKernel k{nullptr, nullptr, loop > ct ? loop : ct, STAGES == 0 ? 256 : 64 * TileWaves<BM, BN>::NW};
+  if constexpr (GROUPED) k.group = gemm_group_kernel<T, TC, TA, TB, BM, BN, STAGES>;
+  else if constexpr (STAGES == 0) k.one = gemm_kernel<T, TC, TA, TB, BM, BN>;
+  else k.one = gemm_dma_kernel<T, TC, TA, TB, BM, BN, STAGES>;
+  return k;
+}
+template <typename T, typename TC, bool TA, bool TB>
+static bool lookup_tile(const GemmInstance& i, GemmKernel& k) {
+#define ETP_X(G, BM_, BN_, S_)                                                                                               \
+  if constexpr (tile_exists<T, TA>(BM_))                                                                                     \
+    if (i.grouped == G && i.BM == BM_ && i.BN == BN_ && i.stages == S_) { k = tile_kernel<T, TC, TA, TB, BM_, BN_, S_, G>(); return true; }
+  ETP_GEMM_INSTANCES(ETP_X)
+#undef ETP_X
+  return false;
+}
 template <typename T, typename TC>
-static int launch_trans(int ta, int tb, const GemmArgs& g, int nbatch, hipStream_t st) {
-  if (!ta && !tb) return launch_tiles<T, TC, false, false>(g, nbatch, st);
-  if (!ta && tb) return launch_tiles<T, TC, false, true>(g, nbatch, st);
-  if (ta && tb) return launch_tiles<T, TC, true, true>(g, nbatch, st);
-  return fail(ETP_ERR_INVALID, "gemm: (A trans, B row) storage pairing is not used on this path");
+static bool lookup_storage(const GemmInstance& i, GemmKernel& k) {
+  if (!i.ta && !i.tb) return lookup_tile<T, TC, false, false>(i, k);
+  if (!i.ta && i.tb) return lookup_tile<T, TC, false, true>(i, k);
+  if (i.ta && i.tb) return lookup_tile<T, TC, true, true>(i, k);
+  return false;
+}
+static bool gemm_lookup(const GemmInstance& i, GemmKernel& k) {
+  if (i.family == GEMM_MM32) return mm32_lookup(i, k);
+  if ((i.family == GEMM_REG) != (i.stages == 0)) return false;
+  if (!i.bf16) return !i.c_bf16 && lookup_storage<float, float>(i, k);
+  return i.c_bf16 ? lookup_storage<bf16_t, bf16_t>(i, k) : lookup_storage<bf16_t, float>(i, k);
+}
+static int not_listed(const GemmInstance& inst) {
+  char nm[96];
+  gemm_instance_name(inst, nm, sizeof(nm));
+  return fail(ETP_ERR_INVALID, std::string("gemm: internal error: the selected instance ") + nm + " is not in the instance list");
+}
+
+// ---- the launcher: one for every family, single and grouped ------------------------------------------------------------------------------
+// gs[0 .. n-1] = the prepared problem(s): &g of a single product (grp == nullptr) or grp->g
+static int launch_instance(const GemmInstance& inst, GemmArgs* gs, int n, GemmGroup* grp, int nbatch, hipStream_t st) {
+  GemmKernel k;
+  if (!gemm_lookup(inst, k)) return not_listed(inst);
+  ETP_CHECK_HIP(ensure_dyn_lds(grp ? reinterpret_cast<const void*>(k.group) : reinterpret_cast<const void*>(k.one), k.lds));
+  const size_t ts = inst.bf16 ? 2 : 4, cs = inst.c_bf16 ? 2 : 4;
+  int tiles = 0;
+  double flops = 0, bytes = 0;
+  for (int i = 0; i < n; ++i) {
+    const GemmArgs& g = gs[i];
+    if (grp) grp->tile_start[i] = tiles;
+    tiles += (int)(inst.family == GEMM_MM32 ? tiles_whole(g, inst.BM, inst.BN) : tiles_up(g, inst.BM, inst.BN));
+    flops += 2.0 * g.M * g.N * g.K * nbatch;
+    bytes += ((double)g.M * g.K + (double)g.N * g.K) * nbatch * ts + (double)g.M * g.N * nbatch * cs;
+  }
+  if (grp)
+    for (int i = n; i <= ETP_GEMM_GROUP_MAX; ++i) grp->tile_start[i] = tiles;
+  const int gy = grp ? 1 : nbatch * gs[0].ksplit;
+  const bool probe = g_probe_buf != nullptr && inst.family != GEMM_REG;      // (the register-staged kernels carry no probe)
+  char nm[96];
+  if (probe || g_prof_on) gemm_instance_name(inst, nm, sizeof(nm));          // nobody listening: no name is formatted
+  unsigned long long* slot = probe ? probe_slot(nm, (long)tiles * gy, gs[0].M, gs[0].N, gs[0].K) : nullptr;
+  for (int i = 0; i < n; ++i) gs[i].dbg = slot;
+  ProfRec rec;
+  const bool prof = g_prof_on && prof_begin(nm, flops, bytes, st, rec);
+  if (grp) ETP_LAUNCH(k.group, dim3(tiles), dim3(k.threads), k.lds, st, *grp);
+  else ETP_LAUNCH(k.one, dim3(tiles, gy, 1), dim3(k.threads), k.lds, st, gs[0]);
+  ETP_CHECK_LAUNCH("gemm");
+  if (prof) prof_end(rec, st);
+  return ETP_OK;
 }
 
 // argument checks + derived fields (xcd_map, vec_epilogue) shared by the single and the grouped launcher
@@ -609,115 +733,14 @@ static int prepare_args(int dtype, int c_dtype, int ta, int tb, const GemmArgs& 
   return ETP_OK;
 }
 
-int launch_gemm(int dtype, int c_dtype, int ta, int tb, const GemmArgs& g_in, int nbatch, hipStream_t st) {
-  GemmArgs g;
+// checks + selection of one product / of a group of n >= 2: everything launch_gemm / launch_gemm_group do short of launching
+static int plan_one(int dtype, int c_dtype, int ta, int tb, const GemmArgs& g_in, int nbatch, GemmArgs& g, GemmInstance& inst) {
   ETP_TRY(prepare_args(dtype, c_dtype, ta, tb, g_in, nbatch, g));
-  if (dtype == ETP_BF16 && !(ta && !tb)) {           // whole-tile bf16 products: the 32x32x16 family (gemm_mm32.hip)
-    const int cls = mm32_class(g, nbatch);
-    if (cls) return launch_mm32(c_dtype, ta, tb, g, cls, st);
-  }
-  if (dtype == ETP_F32) return launch_trans<float, float>(ta, tb, g, nbatch, st);
-  if (c_dtype == ETP_F32) return launch_trans<bf16_t, float>(ta, tb, g, nbatch, st);
-  return launch_trans<bf16_t, bf16_t>(ta, tb, g, nbatch, st);
-}
-
-// ---- grouped launch ---------------------------------------------------------------------------------------------------
-template <typename T, typename TC, bool TA, bool TB, int BM, int BN, int STAGES>
-static int launch_group_one(GemmGroup& grp, hipStream_t st) {
-  using GA = TileGeom<T, TA, BM, 0>;
-  using GB = TileGeom<T, TB, BN, 0>;
-  constexpr int smem_loop = STAGES * (GA::BYTES + GB::BYTES), smem_c = BM * (BN + 4) * 4;
-  constexpr int smem = smem_loop > smem_c ? smem_loop : smem_c;
-  void (*kern)(const GemmGroup) = gemm_group_kernel<T, TC, TA, TB, BM, BN, STAGES>;
-  ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(kern), smem));
-  int tiles = 0;
-  double flops = 0, bytes = 0;
-  for (int i = 0; i < grp.n; ++i) {
-    const GemmArgs& g = grp.g[i];
-    grp.tile_start[i] = tiles;
-    tiles += ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-    flops += 2.0 * g.M * g.N * g.K;
-    bytes += ((double)g.M * g.K + (double)g.N * g.K) * sizeof(T) + (double)g.M * g.N * sizeof(TC);
-  }
-  for (int i = grp.n; i <= ETP_GEMM_GROUP_MAX; ++i) grp.tile_start[i] = tiles;
-  const int grid = tiles;
-  char nm[96];
-  snprintf(nm, sizeof(nm), "gemm_group<%s,%s,%s%s,%dx%d,s%d>", sizeof(T) == 2 ? "bf16" : "f32", sizeof(TC) == 2 ? "bf16" : "f32",
-           TA ? "T" : "N", TB ? "N" : "T", BM, BN, STAGES);
-  {
-    unsigned long long* slot = g_probe_buf ? probe_slot(nm, tiles, grp.g[0].M, grp.g[0].N, grp.g[0].K) : nullptr;
-    for (int i = 0; i < grp.n; ++i) grp.g[i].dbg = slot;
-  }
-  ProfRec rec;
-  const bool prof = g_prof_on && !rec_active() && prof_wanted(nm);
-  if (prof) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    rec.id = prof_id(nm);
-    rec.flops = flops; rec.bytes = bytes;
-    ETP_CHECK_HIP(hipEventCreate(&rec.a));
-    ETP_CHECK_HIP(hipEventCreate(&rec.b));
-    ETP_CHECK_HIP(hipEventRecord(rec.a, st));
-  }
-  ETP_LAUNCH(kern, dim3(grid), dim3(64 * TileWaves<BM, BN>::NW), smem, st, grp);
-  ETP_CHECK_LAUNCH("gemm_group");
-  if (prof) {
-    ETP_CHECK_HIP(hipEventRecord(rec.b, st));
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof_recs.push_back(rec);
-  }
+  if (ta && !tb) return fail(ETP_ERR_INVALID, "gemm: (A trans, B row) storage pairing is not used on this path");
+  inst = gemm_select(dtype, c_dtype, ta, tb, g, nbatch);
   return ETP_OK;
 }
-
-template <typename T, typename TC, bool TA, bool TB>
-static int launch_group_tiles(GemmGroup& grp, hipStream_t st) {
-  long t128 = 0;
-  bool all_big = true;
-  for (int i = 0; i < grp.n; ++i) {
-    t128 += (long)((grp.g[i].M + 127) / 128) * ((grp.g[i].N + 127) / 128);
-    all_big = all_big && grp.g[i].M >= 128 && grp.g[i].N >= 128;
-  }
-  // 128x128 tiles halve the L2->LDS bytes per FLOP; they pay once the group still gives most CUs a tile
-  bool big = all_big && t128 >= 160;
-  // 256x128: forced only (see launch_tiles)
-  bool all_huge = sizeof(T) == 2;
-  for (int i = 0; i < grp.n; ++i) all_huge = all_huge && grp.g[i].M >= 256 && grp.g[i].N >= 128;
-  bool huge = false;
-  int stages = (big || huge) ? 2 : 3;
-  const char* force = opt_str(OPT_GROUP_TILE);          // tuning aid: "256s2", "256s3", "128s2", "128s3", "64s3", "64s4"
-  if (force && force[0]) {
-    huge = force[0] == '2' && all_huge;
-    big = force[0] == '1' && all_big;
-    stages = (big || huge) ? 2 : 3;
-    if (strstr(force, "s2")) stages = 2;
-    if (strstr(force, "s3")) stages = 3;
-    if (strstr(force, "s4")) stages = 4;
-  }
-  if (huge) {
-    if constexpr (sizeof(T) == 2) {
-      if (stages == 3) return launch_group_one<T, TC, TA, TB, 256, 128, 3>(grp, st);
-      return launch_group_one<T, TC, TA, TB, 256, 128, 2>(grp, st);
-    }
-  }
-  if (big) {
-    if (stages == 3) return launch_group_one<T, TC, TA, TB, 128, 128, 3>(grp, st);
-    return launch_group_one<T, TC, TA, TB, 128, 128, 2>(grp, st);
-  }
-  if (stages == 4) return launch_group_one<T, TC, TA, TB, 64, 64, 4>(grp, st);
-  return launch_group_one<T, TC, TA, TB, 64, 64, 3>(grp, st);
-}
-
-template <typename T, typename TC>
-static int launch_group_trans(int ta, int tb, GemmGroup& grp, hipStream_t st) {
-  if (!ta && !tb) return launch_group_tiles<T, TC, false, false>(grp, st);
-  if (!ta && tb) return launch_group_tiles<T, TC, false, true>(grp, st);
-  if (ta && tb) return launch_group_tiles<T, TC, true, true>(grp, st);
-  return fail(ETP_ERR_INVALID, "gemm group: (A trans, B row) storage pairing is not used on this path");
-}
-
-int launch_gemm_group(int dtype, int c_dtype, int ta, int tb, const GemmArgs* gs, int n, hipStream_t st) {
-  ETP_REQUIRE(gs && n >= 1 && n <= ETP_GEMM_GROUP_MAX, "1..ETP_GEMM_GROUP_MAX problems per group");
-  if (n == 1) return launch_gemm(dtype, c_dtype, ta, tb, gs[0], 1, st);
-  GemmGroup grp;
+static int plan_group(int dtype, int c_dtype, int ta, int tb, const GemmArgs* gs, int n, GemmGroup& grp, GemmInstance& inst) {
   memset(&grp, 0, sizeof(grp));
   grp.n = n;
   // longest reduction first: a tile's run time grows with K, and the last-dispatched tiles set the tail of the launch
@@ -728,14 +751,46 @@ int launch_gemm_group(int dtype, int c_dtype, int ta, int tb, const GemmArgs* gs
   for (int i = 0; i < n; ++i) {
     const GemmArgs& gi = gs[order[i]];
     uniform = uniform && gi.K == gs[order[0]].K;
-    ETP_REQUIRE(gi.ksplit == 1 && gemm_uses_dma(dtype, gi.K, 1), "grouped products need unsplit LDS-DMA-able reductions");
+    if (!(gi.ksplit == 1 && gemm_uses_dma(dtype, gi.K, 1)))
+      return fail(ETP_ERR_INVALID, "launch_gemm_group: grouped products need unsplit LDS-DMA-able reductions");
     ETP_TRY(prepare_args(dtype, c_dtype, ta, tb, gi, 1, grp.g[i]));
   }
   grp.xcd_chunks = (uniform && grp.g[0].xcd_map) ? 1 : 0;
-  if (dtype == ETP_BF16 && c_dtype == ETP_F32 && ta && tb && mm32_group_ok(grp)) return launch_mm32_group(grp, st);
-  if (dtype == ETP_F32) return launch_group_trans<float, float>(ta, tb, grp, st);
-  if (c_dtype == ETP_F32) return launch_group_trans<bf16_t, float>(ta, tb, grp, st);
-  return launch_group_trans<bf16_t, bf16_t>(ta, tb, grp, st);
+  if (ta && !tb) return fail(ETP_ERR_INVALID, "gemm group: (A trans, B row) storage pairing is not used on this path");
+  inst = gemm_group_select(dtype, c_dtype, ta, tb, grp);
+  return ETP_OK;
+}
+
+int launch_gemm(int dtype, int c_dtype, int ta, int tb, const GemmArgs& g_in, int nbatch, hipStream_t st) {
+  GemmArgs g;
+  GemmInstance inst;
+  ETP_TRY(plan_one(dtype, c_dtype, ta, tb, g_in, nbatch, g, inst));
+  return launch_instance(inst, &g, 1, nullptr, nbatch, st);
+}
+
+int launch_gemm_group(int dtype, int c_dtype, int ta, int tb, const GemmArgs* gs, int n, hipStream_t st) {
+  ETP_REQUIRE(gs && n >= 1 && n <= ETP_GEMM_GROUP_MAX, "1..ETP_GEMM_GROUP_MAX problems per group");
+  if (n == 1) return launch_gemm(dtype, c_dtype, ta, tb, gs[0], 1, st);
+  GemmGroup grp;
+  GemmInstance inst;
+  ETP_TRY(plan_group(dtype, c_dtype, ta, tb, gs, n, grp, inst));
+  return launch_instance(inst, grp.g, n, &grp, 1, st);
+}
+
+// Host only: the name of the instance launch_gemm (n == 1) / launch_gemm_group (n >= 2) would run, through the same checks, the
+// same selection and the same list lookup.  -> the name's length (written truncated to cap), or the launch's own refusal.
+int gemm_instance_query(int dtype, int c_dtype, int ta, int tb, const GemmArgs* gs, int n, int nbatch, char* out, int cap) {
+  GemmInstance inst;
+  if (n == 1) {
+    GemmArgs g;
+    ETP_TRY(plan_one(dtype, c_dtype, ta, tb, gs[0], nbatch, g, inst));
+  } else {
+    GemmGroup grp;
+    ETP_TRY(plan_group(dtype, c_dtype, ta, tb, gs, n, grp, inst));
+  }
+  GemmKernel k;
+  if (!gemm_lookup(inst, k)) return not_listed(inst);
+  return gemm_instance_name(inst, out, (out && cap > 0) ? cap : 0);
 }
 
 }  // namespace etp

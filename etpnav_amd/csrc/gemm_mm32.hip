@@ -23,7 +23,8 @@
 //     fragments' ds_read_b128 lane groups), transposed operands [k][rows] with  chunk ^= (k & 3) << 2  (128-row tiles) or
 //     ((k >> 1) & 1) << 2  (64-row tiles): the four k-rows one ds_read_b64_tr_b16 lane group touches land on disjoint bank
 //     ranges.  Both swizzles are applied to the DMA source address and the fragment read address (same involution).
-// Only whole tiles: M % BM == 0, N % BN == 0, K % 64 == 0, K >= 128, unbatched, unsplit -- everything else stays on gemm.hip.
+// Only whole tiles: M % BM == 0, N % BN == 0, K % 64 == 0, K >= 128, unbatched, unsplit -- everything else stays on gemm.hip
+// (gemm.hip's gemm_select / gemm_group_select decide; this file holds the kernels and the list of their instances).
 // The fused epilogue (bias, erf-GELU and its backward, ReLU, dropout, residual, accumulate) is the shared one (gemm_shared.h).
 #include <stdlib.h>
 #include <string.h>
@@ -159,7 +160,7 @@ template <int FM, int FN> struct Frags { bf16x8_t a[FM], b[FN]; };
 // of the grouped weight gradient already takes 43 us of the full kernel's 51 (profiles/r04a_mm32_probe_mfma_only.json): the
 // wavefronts' own read + MFMA stream, not the DMA, sets most of the loop time.  A 128x64 wavefront tile reads 6 KiB for
 // 8 MFMAs (96 B/clk per CU) and the 256x128 tile moves 25 % fewer L2 bytes per FLOP, but its single wavefront per SIMD
-// exposes every LDS latency: it only wins on reductions of >= 4096 rows (mm32_group_class below).
+// exposes every LDS latency: it only wins on reductions of >= 4096 rows (gemm_group_select, gemm.hip).
 //
 // KS = 2 (round 6): INTRA-WORKGROUP split of the reduction.  Eight wavefronts; wave group 0 (waves 0-3) reduces the
 // first half of K, wave group 1 (waves 4-7) the second half of the SAME output tile, each through its own ring, and the two fp32
@@ -551,152 +552,46 @@ template <int BM, int BN, int STAGES, int KS = 1> constexpr int smem_bytes() {
   return ring > ct ? ring : ct;
 }
 
-template <typename TC, bool TA, bool TB, int BM, int BN, int STAGES, int KS = 1>
-static int launch(const GemmArgs& g_in, hipStream_t st) {
-  constexpr int smem = smem_bytes<BM, BN, STAGES, KS>();
-  void (*kern)(const GemmArgs) = kernel<TC, TA, TB, BM, BN, STAGES, KS>;
-  ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(kern), smem));
-  const int tiles = (g_in.M / BM) * (g_in.N / BN);
-  GemmArgs g = g_in;
-  char nm[96];
-  snprintf(nm, sizeof(nm), "mm32<bf16,%s,%s%s,%dx%d,s%d%s>", sizeof(TC) == 2 ? "bf16" : "f32", TA ? "T" : "N", TB ? "N" : "T", BM, BN,
-           STAGES, KS == 2 ? ",k2" : "");
-  g.dbg = probe_slot(nm, tiles, g.M, g.N, g.K);
-  ProfRec rec;
-  const bool prof = prof_begin(nm, 2.0 * g.M * g.N * g.K,
-                               ((double)g.M * g.K + (double)g.N * g.K) * 2 + (double)g.M * g.N * sizeof(TC), st, rec);
-  ETP_LAUNCH(kern, dim3(tiles), dim3(256 * KS), smem, st, g);
-  ETP_CHECK_LAUNCH("mm32");
-  if (prof) prof_end(rec, st);
-  return ETP_OK;
-}
-
-template <typename TC, bool TA, bool TB, int BM, int BN, int STAGES>
-static int launch_group(GemmGroup& grp, hipStream_t st) {
-  constexpr int smem = smem_bytes<BM, BN, STAGES>();
-  void (*kern)(const GemmGroup) = group_kernel<TC, TA, TB, BM, BN, STAGES>;
-  ETP_CHECK_HIP(ensure_dyn_lds(reinterpret_cast<const void*>(kern), smem));
-  int tiles = 0;
-  double flops = 0, bytes = 0;
-  for (int i = 0; i < grp.n; ++i) {
-    const GemmArgs& g = grp.g[i];
-    grp.tile_start[i] = tiles;
-    tiles += (g.M / BM) * (g.N / BN);
-    flops += 2.0 * g.M * g.N * g.K;
-    bytes += ((double)g.M * g.K + (double)g.N * g.K) * 2 + (double)g.M * g.N * sizeof(TC);
-  }
-  for (int i = grp.n; i <= ETP_GEMM_GROUP_MAX; ++i) grp.tile_start[i] = tiles;
-  char nm[96];
-  snprintf(nm, sizeof(nm), "mm32_group<bf16,%s,%s%s,%dx%d,s%d>", sizeof(TC) == 2 ? "bf16" : "f32", TA ? "T" : "N", TB ? "N" : "T", BM,
-           BN, STAGES);
-  {
-    unsigned long long* slot = probe_slot(nm, tiles, grp.g[0].M, grp.g[0].N, grp.g[0].K);
-    for (int i = 0; i < grp.n; ++i) grp.g[i].dbg = slot;
-  }
-  ProfRec rec;
-  const bool prof = prof_begin(nm, flops, bytes, st, rec);
-  ETP_LAUNCH(kern, dim3(tiles), dim3(256), smem, st, grp);
-  ETP_CHECK_LAUNCH("mm32_group");
-  if (prof) prof_end(rec, st);
-  return ETP_OK;
-}
-
-// shapes this family takes
-static bool eligible(const GemmArgs& g, int bm, int bn) {
-  return g.M % bm == 0 && g.N % bn == 0 && g.K % 64 == 0 && g.K >= 128 && g.ksplit == 1 && g.vec_epilogue && g.out_mode != 2 &&
-         g.lda % 8 == 0 && g.ldb % 8 == 0;
-}
+// ---- the instance list: every kernel this file instantiates --------------------------------------------------------------------------
+// X(BM, BN, STAGES, KS): each for C in {bf16, f32} and storage in {NT, NN, TN}; KS = 2 (split reduction) with a row-major A only
+#define ETP_MM32_INSTANCES(X) X(128, 128, 2, 1) X(128, 64, 3, 1) X(128, 64, 3, 2) X(128, 64, 2, 2)
+// grouped, X(BM, BN, STAGES): the weight gradients' <float, TN> only
+#define ETP_MM32_GROUP_INSTANCES(X) X(128, 128, 2) X(256, 128, 3)
 
 template <typename TC, bool TA, bool TB>
-static int launch_class(const GemmArgs& g, int cls, hipStream_t st) {
-  if (cls == 128) return launch<TC, TA, TB, 128, 128, 2>(g, st);
-  if constexpr (!TA) {
-    if (cls == 264) return launch<TC, TA, TB, 128, 64, 3, 2>(g, st);   // split reduction, two rings of three (144 KB)
-    if (cls == 262) return launch<TC, TA, TB, 128, 64, 2, 2>(g, st);   // split reduction, two rings of two (96 KB: a 64-KB leaf workgroup fits beside it)
-  }
-  return launch<TC, TA, TB, 128, 64, 3>(g, st);
+static bool lookup_tile(const GemmInstance& i, GemmKernel& k) {
+#define ETP_X(BM_, BN_, S_, KS_)                                                                \
+  if constexpr (KS_ == 1 || !TA)                                                                \
+    if (i.BM == BM_ && i.BN == BN_ && i.stages == S_ && i.ks == KS_) {                          \
+      k = GemmKernel{kernel<TC, TA, TB, BM_, BN_, S_, KS_>, nullptr, smem_bytes<BM_, BN_, S_, KS_>(), 256 * KS_};  \
+      return true;                                                                              \
+    }
+  ETP_MM32_INSTANCES(ETP_X)
+#undef ETP_X
+  return false;
 }
-static bool eligible_k2(const GemmArgs& g) { return eligible(g, 128, 64) && g.K % 128 == 0 && g.K >= 256; }
+template <typename TC>
+static bool lookup_storage(const GemmInstance& i, GemmKernel& k) {
+  if (!i.ta && !i.tb) return lookup_tile<TC, false, false>(i, k);
+  if (!i.ta && i.tb) return lookup_tile<TC, false, true>(i, k);
+  if (i.ta && i.tb) return lookup_tile<TC, true, true>(i, k);
+  return false;
+}
 
 }  // namespace mm32
 
-// 0: not taken (the caller falls back to gemm.hip's kernels), 128 / 64: tile class (128x128 ring 2, 128x64 ring 3).
-// ETP_MM32=0 switches the family off (A/B runs against gemm.hip's kernels); ETP_MM32=128 / 64 forces that class for every
-// eligible product whatever the tile count (tests).
-static int mm32_mode() {
-  return opt_int(OPT_MM32, 1);
-}
-int mm32_class(const GemmArgs& g, int nbatch) {
-  const int mode = mm32_mode();
-  if (!mode || nbatch != 1) return 0;
-  if (mode == 128) return mm32::eligible(g, 128, 128) ? 128 : 0;
-  if (mode == 64) return mm32::eligible(g, 128, 64) ? 64 : 0;
-  if (mode == 264 || mode == 262) return mm32::eligible_k2(g) ? mode : (mm32::eligible(g, 128, 64) ? 64 : 0);
-  const long t128 = (long)(g.M / 128) * (g.N / 128);
-  if (mm32::eligible(g, 128, 128) && t128 >= 320) return 128;
-  // 128x64: the N = 768 products of the M = B*L rows (240 workgroups) and everything between them and the 128x128 class
-  const long tw = (long)(g.M / 128) * (g.N / 64);
-  // one workgroup per CU in ONE resident round (200 .. 256 tiles: the N = 768 products of the 2560 text rows): the split-reduction
-  // form (mm32::tile, KS = 2) puts a second wavefront on every SIMD.  Measured (profiles/r06_k2_bench.txt, r06_ab_runs.json): isolated
-  // launches 3 - 6 % faster with two rings of three (2560x768x3072: 18.5 -> 17.5 us), 20 % SLOWER with two rings of two, and the step
-  // +0.3 % with it (4.054 / 4.056 against 4.043 / 4.038 ms): these loops move 283 MB through the CUs in 13.3 us = 21 TB/s, the rate the
-  // feed bench reaches with nothing but the loads (profiles/r04a_feed_bench.txt) -- they are at the L2 -> CU feed, not waiting on
-  // latency, and a 144-KB workgroup displaces the leaf workgroup that shared its CU.  So: OFF by default; MM32_K2 = 264 / 262 turns the
-  // class on (tests force it through MM32 = 264 / 262).
-  if (mm32::eligible(g, 128, 64) && tw >= 200) {
-    const int k2 = opt_int(OPT_MM32_K2, 0);
-    if (k2 && tw <= 256 && mm32::eligible_k2(g)) return k2 == 262 ? 262 : 264;   // (storage classes with a transposed A keep the 64 class: launch_class)
-    return 64;
+bool mm32_lookup(const GemmInstance& i, GemmKernel& k) {
+  if (i.family != GEMM_MM32 || !i.bf16) return false;
+  if (!i.grouped) return i.c_bf16 ? mm32::lookup_storage<bf16_t>(i, k) : mm32::lookup_storage<float>(i, k);
+  if (i.c_bf16 || !i.ta || !i.tb || i.ks != 1) return false;
+#define ETP_X(BM_, BN_, S_)                                                                      \
+  if (i.BM == BM_ && i.BN == BN_ && i.stages == S_) {                                            \
+    k = GemmKernel{nullptr, mm32::group_kernel<float, true, true, BM_, BN_, S_>, mm32::smem_bytes<BM_, BN_, S_>(), 256};  \
+    return true;                                                                                 \
   }
-  return 0;
-}
-
-// C dtype: bf16 or fp32; operands bf16.  `cls` from mm32_class.
-int launch_mm32(int c_dtype, int ta, int tb, const GemmArgs& g, int cls, hipStream_t st) {
-  if (c_dtype == ETP_F32) {
-    if (!ta && !tb) return mm32::launch_class<float, false, false>(g, cls, st);
-    if (!ta && tb) return mm32::launch_class<float, false, true>(g, cls, st);
-    if (ta && tb) return mm32::launch_class<float, true, true>(g, cls, st);
-  } else {
-    if (!ta && !tb) return mm32::launch_class<bf16_t, false, false>(g, cls, st);
-    if (!ta && tb) return mm32::launch_class<bf16_t, false, true>(g, cls, st);
-    if (ta && tb) return mm32::launch_class<bf16_t, true, true>(g, cls, st);
-  }
-  return fail(ETP_ERR_INVALID, "mm32: (A trans, B row) storage pairing is not used on this path");
-}
-
-// grouped weight gradients (TN, fp32 out): true when every problem of the group is whole 128x128 tiles
-bool mm32_group_ok(const GemmGroup& grp) {
-  if (!mm32_mode()) return false;
-  long t = 0;
-  for (int i = 0; i < grp.n; ++i) {
-    if (!mm32::eligible(grp.g[i], 128, 128)) return false;
-    t += (long)(grp.g[i].M / 128) * (grp.g[i].N / 128);
-  }
-  return t >= 100 || mm32_mode() == 128;
-}
-// 256x128 tiles (one workgroup per CU, 128x64 per wavefront) when every problem is whole 256x128 tiles, the reduction is long
-// enough to pay for a tile that has the CU to itself (no second workgroup covers its fill, its epilogue and -- with one
-// wavefront per SIMD -- the latency of its ds_read_b64_tr_b16 fragment reads) and the list still covers most of the chip.
-// Measured (tools/experiments/r04_group_class_probe.py, one text layer's four products, us per launch, 128x128 / 256x128):
-// 512 tokens 18.1 / 24.6, 1152: 29.0 / 34.4, 2560: 51.4 / 61.8, 8192: 148.8 / 143.5 -- only the 8192-token reductions of
-// BASELINE config 4 take it.  ETP_MM32_GROUP=128 / 256 forces a class (tests, A/B runs).
-static int mm32_group_class(const GemmGroup& grp) {
-  const int force = opt_int(OPT_MM32_GROUP, 0);
-  if (force == 128) return 128;
-  long t = 0;
-  int kmin = 1 << 30;
-  for (int i = 0; i < grp.n; ++i) {
-    if (!mm32::eligible(grp.g[i], 256, 128)) return 128;
-    t += (long)(grp.g[i].M / 256) * (grp.g[i].N / 128);
-    kmin = grp.g[i].K < kmin ? grp.g[i].K : kmin;
-  }
-  if (force == 256) return 256;
-  return (kmin >= 4096 && t >= 160) ? 256 : 128;
-}
-int launch_mm32_group(GemmGroup& grp, hipStream_t st) {
-  if (mm32_group_class(grp) == 256) return mm32::launch_group<float, true, true, 256, 128, 3>(grp, st);
-  return mm32::launch_group<float, true, true, 128, 128, 2>(grp, st);
+  ETP_MM32_GROUP_INSTANCES(ETP_X)
+#undef ETP_X
+  return false;
 }
 
 }  // namespace etp

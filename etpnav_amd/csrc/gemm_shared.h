@@ -437,10 +437,21 @@ void prof_end(const ProfRec& rec, hipStream_t st);
 // device buffer slot of the next probed launch (nullptr: probe off / full / recording a graph)
 unsigned long long* probe_slot(const char* name, long wgs, int M, int N, int K);
 
-// ---- gemm_mm32.hip: bf16 tiles on 32x32x16 MFMAs with the order-pinned main loop (whole tiles only) ---------------------------
-int mm32_class(const GemmArgs& g, int nbatch);       // 0: not taken; else the tile class to pass to launch_mm32 (g = prepared args)
-int launch_mm32(int c_dtype, int ta, int tb, const GemmArgs& g, int cls, hipStream_t st);
-bool mm32_group_ok(const GemmGroup& grp);            // TN fp32-out group of whole 128x128 tiles
-int launch_mm32_group(GemmGroup& grp, hipStream_t st);
+// ---- instance selection, list and launcher (gemm.hip; the mm32 kernels' list sits beside them in gemm_mm32.hip) ------------------------
+// One kernel instance of the GEMM library.  Its name -- gemm_instance_name, e.g. `gemm_dma<bf16,f32,TN,64x64,s3>` or
+// `mm32<bf16,bf16,NT,128x64,s3,k2>` -- is what the profiler, the phase probe and etp_gemm_instance report.
+enum GemmFamily { GEMM_REG, GEMM_DMA, GEMM_MM32 };   // register-staged `gemm`, LDS-DMA `gemm_dma` / `gemm_group`, `mm32` / `mm32_group`
+struct GemmInstance {
+  int family;
+  bool grouped, bf16, c_bf16, ta, tb;                // operand / C dtype (bf16 or fp32), operand storage
+  int BM, BN, stages, ks;                            // tile, ring depth (0: register-staged), intra-workgroup reduction split (1 or 2)
+};
+// Pure functions of the prepared arguments and the switches: no HIP call, nothing launched.
+GemmInstance gemm_select(int dtype, int c_dtype, int ta, int tb, const GemmArgs& g, int nbatch);
+GemmInstance gemm_group_select(int dtype, int c_dtype, int ta, int tb, const GemmGroup& grp);
+int gemm_instance_name(const GemmInstance& i, char* out, int cap);     // snprintf semantics
+// what an instance list maps an instance to: the kernel (single or grouped signature), its dynamic LDS bytes and workgroup size
+struct GemmKernel { void (*one)(const GemmArgs); void (*group)(const GemmGroup); int lds, threads; };
+bool mm32_lookup(const GemmInstance& i, GemmKernel& k);                // gemm_mm32.hip's list; false: not instantiated
 
 }  // namespace etp

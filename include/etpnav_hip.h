@@ -108,6 +108,14 @@ int etp_gemm(const etp_gemm_desc* d, etp_stream_t stream);
  * four to seven weight gradients of one transformer layer (autograd of vilmodel_cmt.py:108-110,151,178,190,326-328), none
  * of which fills 256 CUs alone.  Every K must be a multiple of the 128-byte slab (64 bf16 / 32 fp32) and >= 2 slabs. */
 int etp_gemm_group(const etp_gemm_desc* d, int n, etp_stream_t stream);
+/* Host only, launches nothing and makes no HIP call: the name of the kernel instance etp_gemm(d) (n == 1) or etp_gemm_group(d, n)
+ * (n > 1; the members re-sorted by K as the launch does) would run under the current switches, e.g. `gemm_dma<bf16,f32,TN,64x64,s3>`
+ * or `mm32<bf16,bf16,NT,128x64,s3,k2>` -- family<operand dtype, C dtype, storage, tile, ring depth[, k2]>, the name the per-launch
+ * profiler (etp_prof_report) and the phase probe report.  It runs the launch's own argument checks, instance selection and instance-list
+ * lookup; pointers are only tested for NULL and alignment, never dereferenced.  Returns the name's length and writes the name, truncated to
+ * `cap` bytes with the terminator (out may be NULL); where the launch would refuse the call, that same error code, with the same
+ * etp_last_error. */
+int etp_gemm_instance(const etp_gemm_desc* d, int n, char* out, int cap);
 
 /* db[n] += sum_m dY[m,n]  (bias gradient of every nn.Linear).  db ACCUMULATES.  N % 4 == 0 and ld % 4 == 0; dy aligned to four
  * elements (8 bytes bf16, 16 bytes fp32); columns [N, ld) are never read.  Anything else: ETP_ERR_INVALID, nothing launched. */

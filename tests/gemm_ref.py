@@ -335,3 +335,99 @@ def shape_matrix():
         out |= {(M, N, K // 2, False), (M, N, 128, False)}
     out |= {(128, 64, 3072, True), (256, 128, 3072, True), (256, 128, 3072, False), (256, 64, 3072, True)}
     return sorted(out)
+
+
+# ---- the instance lists (tests/test_gemm_kernels_gpu.py launches them, tests/test_gemm_dispatch_cpu.py asks etp_gemm_instance for them) ----
+STOR = ((0, 0), (0, 1), (1, 1))                       # (trans_a, trans_b): NT, NN, TN
+
+
+def tname(bf16):
+    return "bf16" if bf16 else "f32"
+
+
+def sname(ta, tb):
+    return ("T" if ta else "N") + ("N" if tb else "T")
+
+
+def inst(kind, bf16, c_bf16, ta, tb, BM, BN, S, k2=False):
+    return f"{kind}<{tname(bf16)},{tname(c_bf16)},{sname(ta, tb)},{BM}x{BN},s{S}{',k2' if k2 else ''}>"
+
+
+def c_of(ta, tb, bf16):
+    """output dtype an instance is listed with: weight gradients (TN) of bf16 operands leave fp32, everything else the operand dtype"""
+    return bf16 and not (ta and tb)
+
+
+REG = [dict(name=inst("gemm", bf, cb, ta, tb, bm, bm, 0), opts={"GEMM_TILE": f"{bm}r", "MM32": "0"}, BM=bm, BN=bm, S=0, ta=ta, tb=tb,
+            bf16=bf, c_bf16=cb, kind="reg")
+       for bm in (64, 128) for bf, cb in ((True, True), (True, False), (False, False)) for ta, tb in STOR]
+DMA = [dict(name=inst("gemm_dma", True, c_of(ta, tb, True), ta, tb, bm, bn, s), opts={"GEMM_TILE": t, "MM32": "0"}, BM=bm, BN=bn, S=s,
+            ta=ta, tb=tb, bf16=True, c_bf16=c_of(ta, tb, True), kind="dma")
+       for t, bm, bn, s in DMA_CLASSES for ta, tb in STOR if not (t == "32" and ta)]
+DMA += [dict(name=inst("gemm_dma", False, False, ta, tb, bm, bn, s), opts={"GEMM_TILE": t, "MM32": "0"}, BM=bm, BN=bn, S=s, ta=ta, tb=tb,
+             bf16=False, c_bf16=False, kind="dma")
+        for t, bm, bn, s in DMA_CLASSES if t in DMA_CLASSES_F32 for ta, tb in STOR]
+MM32 = [dict(name=inst("mm32", True, cb, ta, tb, bm, bn, s, k2), opts={"MM32": c}, BM=bm, BN=bn, S=s, ta=ta, tb=tb, bf16=True, c_bf16=cb,
+             kind="mm32k2" if k2 else "mm32")
+        for c, bm, bn, s, k2 in MM32_CLASSES for cb in (True, False) for ta, tb in STOR if not (k2 and ta)]
+GROUP_CLASSES = [("64s3", 64, 64, 3), ("64s4", 64, 64, 4), ("128s2", 128, 128, 2), ("128s3", 128, 128, 3), ("256s2", 256, 128, 2),
+                 ("256s3", 256, 128, 3)]
+GROUPS = [dict(name=inst("gemm_group", True, False, 1, 1, bm, bn, s), opts={"GROUP_TILE": t, "MM32": "0"}, BM=bm, BN=bn, ta=1, tb=1,
+               bf16=True, c_bf16=False) for t, bm, bn, s in GROUP_CLASSES]
+GROUPS += [dict(name=inst("gemm_group", False, False, 1, 1, 64, 64, 3), opts={"GROUP_TILE": "64s3"}, BM=64, BN=64, ta=1, tb=1, bf16=False,
+                c_bf16=False),
+           dict(name=inst("gemm_group", True, True, 0, 0, 64, 64, 3), opts={"GROUP_TILE": "64s3", "MM32": "0"}, BM=64, BN=64, ta=0, tb=0,
+                bf16=True, c_bf16=True)]
+MM32_GROUPS = [dict(name=inst("mm32_group", True, False, 1, 1, 128, 128, 2), opts={"MM32": "128", "MM32_GROUP": "128"}, BM=128, BN=128,
+                    ta=1, tb=1, bf16=True, c_bf16=False, whole=True),
+               dict(name=inst("mm32_group", True, False, 1, 1, 256, 128, 3), opts={"MM32": "128", "MM32_GROUP": "256"}, BM=256, BN=128,
+                    ta=1, tb=1, bf16=True, c_bf16=False, whole=True)]
+SINGLES = REG + DMA + MM32
+GEMM_SWITCHES = ("GEMM_TILE", "MM32", "MM32_GROUP", "GROUP_TILE", "GEMM_XCD", "MM32_K2", "GEMM_WIDE", "GEMM_SMALL")
+
+
+# ---- dispatch records (tests/golden/gemm_dispatch.json; tools/record_gemm_dispatch.py writes them, test_gemm_dispatch_cpu.py reads them) --
+def rup(x, m):
+    return (x + m - 1) // m * m
+
+
+def dispatch_rec(M, N, K, ta=0, tb=0, bf16=True, c_bf16=None, batch=1, ksplit=1, act=ACT_NONE, out_mode=0, bias=False, R=False, Z=False,
+                 colsum=False, lda=None, ldb=None, ldc=None, ldr=None, ldz=None):
+    """one product as a plain dict of descriptor fields (leading dimensions default to the chunk-rounded extents)"""
+    epc = 8 if bf16 else 4
+    return dict(M=M, N=N, K=K, ta=ta, tb=tb, bf16=bool(bf16), c_bf16=bool(bf16 if c_bf16 is None else c_bf16), batch=batch, ksplit=ksplit,
+                act=act, out_mode=out_mode, bias=bool(bias), R=bool(R), Z=bool(Z), colsum=bool(colsum),
+                lda=lda or (rup(M, epc) if ta else rup(K, epc)), ldb=ldb or (rup(N, epc) if tb else rup(K, epc)), ldc=ldc or N,
+                ldr=(ldr or ldc or N) if R else 0, ldz=(ldz or ldc or N) if Z else 0)
+
+
+def dispatch_pack(r):
+    """the record without its zero / False fields (the fixture's form); dispatch_unpack restores them"""
+    return {k: v for k, v in r.items() if v not in (0, False)}
+
+
+def dispatch_unpack(p):
+    return dict(dispatch_rec(1, 1, 0), ta=0, tb=0, bf16=False, c_bf16=False, batch=0, ksplit=0, M=0, N=0, lda=0, ldb=0, ldc=0) | p
+
+
+def dispatch_extents(r):
+    """elements each buffer of a record spans: A, B, C, R, Z (bias: N, a_colsum: M)"""
+    nb = max(r["batch"], 1)
+    a = (r["K"] if r["ta"] else r["M"]) * r["lda"]
+    b = (r["K"] if r["tb"] else r["N"]) * r["ldb"]
+    return dict(A=max(a, 1), B=max(b, 1), C=nb * r["M"] * r["ldc"], R=r["M"] * r["ldr"], Z=r["M"] * r["ldz"])
+
+
+def dispatch_desc(d, r, ptr):
+    """fill the GemmDesc `d` from record `r`; ptr(name) -> the address of that buffer (16-byte aligned, or whatever the caller means to test)"""
+    d.A, d.B, d.C = ptr("A"), ptr("B"), ptr("C")
+    d.M, d.N, d.K, d.lda, d.ldb, d.ldc = r["M"], r["N"], r["K"], r["lda"], r["ldb"], r["ldc"]
+    d.trans_a, d.trans_b, d.dtype, d.c_dtype = r["ta"], r["tb"], 1 if r["bf16"] else 0, 1 if r["c_bf16"] else 0
+    d.batch, d.batch_inner, d.ksplit, d.alpha = r["batch"], 1, r["ksplit"], 1.0
+    d.sCo = r["M"] * r["ldc"] if r["batch"] > 1 else 0           # batched records: every entry on the same operands, its own C
+    d.bias = ptr("bias") if r["bias"] else None
+    d.R, d.ldr = (ptr("R"), r["ldr"]) if r["R"] else (None, 0)
+    d.Z, d.ldz = (ptr("Z"), r["ldz"]) if r["Z"] else (None, 0)
+    d.act, d.out_mode = r["act"], r["out_mode"]
+    d.a_colsum = ptr("colsum") if r["colsum"] else None
+    return d

@@ -29,7 +29,7 @@ from tests import gemm_ref as gr  # noqa: E402
 DEV = "cuda"
 BF, F32 = _lib.ETP_BF16, _lib.ETP_F32
 NAN = float("nan")
-STOR = ((0, 0), (0, 1), (1, 1))                       # (trans_a, trans_b): NT, NN, TN
+STOR = gr.STOR                                        # (trans_a, trans_b): NT, NN, TN
 assert (gr.ACT_GELU, gr.ACT_RELU, gr.ACT_GELU_BWD, gr.ACT_RELU_BWD, gr.ACT_GELU_SAVEGRAD, gr.ACT_MUL_Z) == \
     (_lib.ACT_GELU, _lib.ACT_RELU, _lib.ACT_GELU_BWD, _lib.ACT_RELU_BWD, _lib.ACT_GELU_SAVEGRAD, _lib.ACT_MUL_Z)
 
@@ -56,16 +56,7 @@ def rup(x, m):
     return (x + m - 1) // m * m
 
 
-def tname(bf16):
-    return "bf16" if bf16 else "f32"
-
-
-def sname(ta, tb):
-    return ("T" if ta else "N") + ("N" if tb else "T")
-
-
-def inst(kind, bf16, c_bf16, ta, tb, BM, BN, S, k2=False):
-    return f"{kind}<{tname(bf16)},{tname(c_bf16)},{sname(ta, tb)},{BM}x{BN},s{S}{',k2' if k2 else ''}>"
+inst = gr.inst
 
 
 def set_opts(etp_opt, opts):
@@ -112,7 +103,15 @@ def z_dtype(act, bf16):
     return torch.float16 if act in (gr.ACT_GELU_SAVEGRAD, gr.ACT_MUL_Z) else torch.bfloat16
 
 
+def asked(descs, n):
+    """etp_gemm_instance: the name the host-side query gives for what is about to be launched"""
+    buf = ctypes.create_string_buffer(96)
+    rc = L().etp_gemm_instance(descs, n, buf, 96)
+    return buf.value.decode() if rc >= 0 else (rc, L().etp_last_error())
+
+
 def launch(d, expect, what):
+    assert asked(ctypes.byref(d), 1) == expect, f"{what}: etp_gemm_instance names {asked(ctypes.byref(d), 1)}"
     with _lib.profiled() as p:
         rc = L().etp_gemm(ctypes.byref(d), stream())
         torch.cuda.synchronize()
@@ -190,38 +189,8 @@ def run_case(expect, M, N, K, ta, tb, bf16, c_bf16, alpha=1.0, bias=False, R=Fal
 
 
 # ---- the instance list ------------------------------------------------------------------------------------------------------------
-def c_of(ta, tb, bf16):
-    """output dtype an instance is listed with: weight gradients (TN) of bf16 operands leave fp32, everything else the operand dtype"""
-    return bf16 and not (ta and tb)
-
-
-REG = [dict(name=inst("gemm", bf, cb, ta, tb, bm, bm, 0), opts={"GEMM_TILE": f"{bm}r", "MM32": "0"}, BM=bm, BN=bm, S=0, ta=ta, tb=tb,
-            bf16=bf, c_bf16=cb, kind="reg")
-       for bm in (64, 128) for bf, cb in ((True, True), (True, False), (False, False)) for ta, tb in STOR]
-DMA_CLASSES = gr.DMA_CLASSES
-DMA = [dict(name=inst("gemm_dma", True, c_of(ta, tb, True), ta, tb, bm, bn, s), opts={"GEMM_TILE": t, "MM32": "0"}, BM=bm, BN=bn, S=s,
-            ta=ta, tb=tb, bf16=True, c_bf16=c_of(ta, tb, True), kind="dma")
-       for t, bm, bn, s in DMA_CLASSES for ta, tb in STOR if not (t == "32" and ta)]
-DMA += [dict(name=inst("gemm_dma", False, False, ta, tb, bm, bn, s), opts={"GEMM_TILE": t, "MM32": "0"}, BM=bm, BN=bn, S=s, ta=ta, tb=tb,
-             bf16=False, c_bf16=False, kind="dma")
-        for t, bm, bn, s in DMA_CLASSES if t in gr.DMA_CLASSES_F32 for ta, tb in STOR]
-MM32_CLASSES = gr.MM32_CLASSES
-MM32 = [dict(name=inst("mm32", True, cb, ta, tb, bm, bn, s, k2), opts={"MM32": c}, BM=bm, BN=bn, S=s, ta=ta, tb=tb, bf16=True, c_bf16=cb,
-             kind="mm32k2" if k2 else "mm32")
-        for c, bm, bn, s, k2 in MM32_CLASSES for cb in (True, False) for ta, tb in STOR if not (k2 and ta)]
-GROUP_CLASSES = [("64s3", 64, 64, 3), ("64s4", 64, 64, 4), ("128s2", 128, 128, 2), ("128s3", 128, 128, 3), ("256s2", 256, 128, 2),
-                 ("256s3", 256, 128, 3)]
-GROUPS = [dict(name=inst("gemm_group", True, False, 1, 1, bm, bn, s), opts={"GROUP_TILE": t, "MM32": "0"}, BM=bm, BN=bn, ta=1, tb=1,
-               bf16=True, c_bf16=False) for t, bm, bn, s in GROUP_CLASSES]
-GROUPS += [dict(name=inst("gemm_group", False, False, 1, 1, 64, 64, 3), opts={"GROUP_TILE": "64s3"}, BM=64, BN=64, ta=1, tb=1, bf16=False,
-                c_bf16=False),
-           dict(name=inst("gemm_group", True, True, 0, 0, 64, 64, 3), opts={"GROUP_TILE": "64s3", "MM32": "0"}, BM=64, BN=64, ta=0, tb=0,
-                bf16=True, c_bf16=True)]
-MM32_GROUPS = [dict(name=inst("mm32_group", True, False, 1, 1, 128, 128, 2), opts={"MM32": "128", "MM32_GROUP": "128"}, BM=128, BN=128,
-                    ta=1, tb=1, bf16=True, c_bf16=False, whole=True),
-               dict(name=inst("mm32_group", True, False, 1, 1, 256, 128, 3), opts={"MM32": "128", "MM32_GROUP": "256"}, BM=256, BN=128,
-                    ta=1, tb=1, bf16=True, c_bf16=False, whole=True)]
-SINGLES = REG + DMA + MM32
+# (tests/gemm_ref.py holds the lists: tests/test_gemm_dispatch_cpu.py asks etp_gemm_instance for the same instances without a GPU)
+REG, DMA, MM32, GROUPS, MM32_GROUPS, SINGLES = gr.REG, gr.DMA, gr.MM32, gr.GROUPS, gr.MM32_GROUPS, gr.SINGLES
 ids = lambda xs: [x["name"] for x in xs]
 
 
@@ -474,6 +443,7 @@ def test_groups(c, n, etp_opt):
                 Cg.view.copy_(C0) if out_mode else Cg.view.fill_(NAN)
                 if Sg is not None:
                     Sg.view.copy_(s_old)
+            assert asked(descs, n) == c["name"], f"{what}: etp_gemm_instance names {asked(descs, n)}"
             with _lib.profiled() as p:
                 rc = L().etp_gemm_group(descs, n, stream())
                 torch.cuda.synchronize()

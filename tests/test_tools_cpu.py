@@ -113,7 +113,7 @@ def test_lds_dma_m0_discipline_scanner():
 
 
 def test_forcing_a_gemm_tile_class_switches_the_mm32_family_off():
-    """_lib.force_gemm_tile: mm32_class is consulted before gemm.hip's tile choice, so a forced gemm.hip class must come
+    """_lib.force_gemm_tile: gemm_select tries the mm32 family before gemm.hip's tile classes, so a forced gemm.hip class must come
     with MM32=0 or eligible bf16 products keep running the mm32 kernel; "auto" hands both choices back to the library.  Round 6: the
     switches live in the library's own table (csrc/options.h, `etp_option_set`), not in os.environ."""
     from etpnav_amd import _lib

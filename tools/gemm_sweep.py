@@ -5,7 +5,7 @@
 Every variant runs the same launch sequence over NSETS rotating operand sets (~80 MB in total: L2-cold, Infinity-Cache
 warm -- what a real step sees: activations were just written by another kernel, weights come from HBM/MALL), timed with
 HIP events over the whole sequence.  Output: JSON {shape key: {variant: us}} + the best variant per shape, which
-csrc/gemm.hip's dispatch table (launch_tiles) is written from.  Also a K sweep at fixed M, N: the intercept at K -> 0 is
+csrc/gemm.hip's tile rules (gemm_select) are written from.  Also a K sweep at fixed M, N: the intercept at K -> 0 is
 the fixed cost of a launch (dispatch + prologue latency + epilogue), the slope the streaming rate.
 """
 import ctypes, json, os, sys
