@@ -14,11 +14,10 @@
 // Heading features avoid arcsin: calculate_vp_rel_pos_fts (:21-44) defines heading0 by sin = -dx/xz, cos = -+|dz|/xz, so
 // sin/cos of (2*pi - (heading0 - base)) follow from the angle-difference identities at full fp32 accuracy.
 #include "kernels.h"
+#include "graph_front.h"
 
 namespace etp {
 
-constexpr int GN = 64;      // max visited nodes per episode
-constexpr int GM = 192;     // max ghost nodes per episode
 constexpr float G_MAX_DIST = 30.f, G_MAX_STEP = 10.f;   // graph_utils.py:9-10
 
 struct GmapArgs {
@@ -76,13 +75,8 @@ __global__ __launch_bounds__(256) void gmap_assemble_kernel(const GmapArgs a) {
   // nearest front of every ghost (first minimum in list order, graph_utils.py:259-270)
   for (int g = tid; g < m; g += 256) {
     const int32_t* fp = a.front_ptr + (long)b * (a.Mmax + 1);
-    float best = 10000.f; int bv = 0;
-    for (int q = fp[g]; q < fp[g + 1]; ++q) {
-      const int f = a.front_idx[(long)b * a.Fmax + q];
-      const float dx = npos[f][0] - gpos[g][0], dy = npos[f][1] - gpos[g][1], dz = npos[f][2] - gpos[g][2];
-      const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-      if (d < best) { best = d; bv = f; }
-    }
+    float best; int bv;
+    nearest_front(a.front_idx + (long)b * a.Fmax, fp[g], fp[g + 1], npos, gpos[g], best, bv);
     fd[g] = best; fv[g] = bv;
   }
   __syncthreads();

@@ -61,6 +61,7 @@ class GraphMapLite:
         self.ghost_embeds: Dict[str, list] = {}
         self.ghost_fronts: Dict[str, list] = {}
         self.ghost_real_pos: Dict[str, list] = {}
+        self.node_stop_scores: Dict[str, float] = {}         # viewpoint -> stop probability (graph_utils.py:161); decide.py fills it
         self.has_real_pos, self.merge_ghost, self.ghost_aug, self.loc_noise = has_real_pos, merge_ghost, ghost_aug, loc_noise
         self.rng = rng if rng is not None else np.random
 
@@ -225,8 +226,10 @@ def pack_batch(episodes: Sequence[dict]) -> Dict[str, np.ndarray]:
     return out
 
 
-def assemble_on_device(batch: Dict[str, np.ndarray], device, G: Optional[int] = None) -> Dict[str, torch.Tensor]:
-    """One H2D copy per compact array + one kernel.  Raises without the HIP library / a GPU (no CPU fallback)."""
+def assemble_on_device(batch: Dict[str, np.ndarray], device, G: Optional[int] = None,
+                       keep_compact: bool = False) -> Dict[str, torch.Tensor]:
+    """One H2D copy per compact array + one kernel.  Raises without the HIP library / a GPU (no CPU fallback).
+    ``keep_compact``: also return the uploaded compact tensors (plus ``_dims``) under ``"compact"``, for ``decide.RolloutDecider``."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.EtpError("etp_gmap_assemble needs an MI355X (cuda/hip device); no CPU fallback exists")
@@ -249,14 +252,18 @@ def assemble_on_device(batch: Dict[str, np.ndarray], device, G: Optional[int] = 
                               ptr(t["cur_heading"]), B, Nmax, Mmax, Fmax, G, ptr(out["gmap_step_ids"]), ptr(out["gmap_masks"]),
                               ptr(out["gmap_visited_masks"]), ptr(out["gmap_pos_fts"]), ptr(out["gmap_pair_dists"]),
                               torch.cuda.current_stream(dev).cuda_stream), "etp_gmap_assemble")
+    if keep_compact:
+        out["compact"] = dict(t, _dims=batch["_dims"])
     return out
 
 
-def nav_gmap_variable(gmaps: Sequence, cur_vp: Sequence[str], cur_pos, cur_heading: Sequence[float], device) -> dict:
+def nav_gmap_variable(gmaps: Sequence, cur_vp: Sequence[str], cur_pos, cur_heading: Sequence[float], device,
+                      keep_compact: bool = False) -> dict:
     """Drop-in for RLTrainer._nav_gmap_variable (ss_trainer_ETP.py:344-417) minus ``gmap_img_fts`` (see module docstring);
-    ``cur_heading[i]`` replaces ``cur_ori[i]`` (= heading_from_quaternion(cur_ori[i]))."""
+    ``cur_heading[i]`` replaces ``cur_ori[i]`` (= heading_from_quaternion(cur_ori[i])).  ``keep_compact``: the uploaded compact
+    tensors come back under ``"compact"`` (pop it before the dict goes to the policy) for ``decide.RolloutDecider.decide``."""
     eps = [pack_episode(g, cur_vp[i], cur_pos[i], cur_heading[i]) for i, g in enumerate(gmaps)]
-    out = assemble_on_device(pack_batch(eps), device)
+    out = assemble_on_device(pack_batch(eps), device, keep_compact=keep_compact)
     out["gmap_vp_ids"] = [[None] + list(g.node_pos.keys()) + list(g.ghost_pos.keys()) for g in gmaps]
     out["no_vp_left"] = [len(g.ghost_pos) == 0 for g in gmaps]
     return out

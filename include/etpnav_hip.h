@@ -626,6 +626,52 @@ int etp_vp_gather(const float* cand_fts, const int32_t* cand_ptr, const float* p
                   const uint8_t* cand_mask, int B, int P, int F, int V, float* out_fts, int64_t* nav_types, int64_t* view_lens,
                   etp_stream_t stream);
 
+/* The rollout decision: from the node logits of forward_navigation to everything envs.step needs, in one launch
+ * (vlnce_baselines/ss_trainer_ETP.py:880-977; GraphMap.shortest_path / front_to_ghost_dist / node_stop_scores,
+ * vlnce_baselines/models/graph_utils.py:161,256,259-270).  One workgroup per episode b; n = n_nodes[b], m = n_ghost[b]:
+ *   node_pos, n_nodes, adj, ghost_pos, n_ghost, front_ptr, front_idx, cur_node: the compact arrays of etp_gmap_assemble (same
+ *     layout, same limits: Nmax <= 64, Mmax <= 192, so G <= 257); ghost arrays may be NULL when Mmax == 0.
+ *   logits [B,G] fp32 (global_logits; entries past 1 + n + m are expected to be -inf, as the masks make them).
+ *   slot [B]: the episode's row of stop_scores = its original environment index (the reference pops paused environments,
+ *     :1036-1044; rows of other slots are never touched).  Slots of one call must differ.
+ *   stop_scores [S,64] fp32, device resident for the whole rollout, -inf at its start: GraphMap.node_stop_scores.
+ *   uniforms [B,2] fp32 in [0,1) or NULL; teacher [B] int64 or NULL; sample_ratio; force_stop (stepk == max_len - 1, :909).
+ * Steps:
+ *   1. p = softmax(logits[b]) in fp32 with the row maximum subtracted (expf; a -inf logit gives exactly 0); stop_prob = p[0]
+ *      (:880-882).  The sum is a tree: <= 2 entries per thread, a 64-lane butterfly, four wave sums -- an addition chain of 10.
+ *   2. greedy = arg-max of the logits, the LOWEST index among equal maxima (:900, torch's rule).
+ *   3. action: uniforms NULL -> greedy.  Otherwise (:896-898) the inverse CDF at u0 = uniforms[b,0]: the first index whose inclusive
+ *      prefix sum of p, added serially in index order, exceeds u0 * total (total = the same serial sum) -- the convention of
+ *      etp_waypoint_tail; it reproduces the distribution of torch.distributions.Categorical, not its random stream -- clamped to the
+ *      last index with p > 0; then, if teacher is given and u1 = uniforms[b,1] <= sample_ratio, the teacher label as it is
+ *      (ignore_index included; labels outside int32 become INT32_MIN).
+ *   4. stop_scores[slot[b], cur_node[b]] = stop_prob; stop_node = arg-max of stop_scores[slot[b], 0 .. n-1], the LOWEST index among
+ *      equal maxima (np.argmax over the insertion-ordered dict, :911-913).
+ *   5. stop if action == 0 or force_stop or m == 0 (:909).  Otherwise ghost = action - 1 - n and front = that ghost's nearest
+ *      front, the FIRST minimum in list order (graph_utils.py:259-270), by the arithmetic etp_gmap_assemble uses (one shared device
+ *      function).  A non-stop action outside [1 + n, 1 + n + m) sets ETP_DECIDE_ERR_ACTION.
+ *   6. target = stop_node on a stop, front otherwise; path = the shortest path cur_node -> target over the visited-node graph
+ *      without its first node (:916-917, 958-959; length 0 when target == cur_node); among equally short paths the predecessor with
+ *      the lowest index wins at every node.  An unreachable target sets ETP_DECIDE_ERR_UNREACHABLE.
+ * record [B, ETP_DECIDE_HDR + Nmax] int32, one contiguous row per episode:
+ *   [0] action  [1] greedy action  [2] flags (ETP_DECIDE_*)  [3] stop node  [4] target node (-1: none)  [5] ghost (-1 on a stop)
+ *   [6] path length  [7] the bits of stop_prob (fp32)  [8 ..] the path's node indices, -1 beyond its length.
+ *   An episode whose n, m, cur_node, slot or fronts are out of range, or with 1 + n + m > G, gets ETP_DECIDE_ERR_INPUT, -1 in the
+ *   other fields, and its table row is left alone.  The host raises on any error flag.
+ * Plain stores only, no atomics: a second run from the same table state returns the same bits.
+ * ETP_ERR_INVALID before anything is launched: B <= 0; G outside 1 .. 257, Nmax outside 1 .. 64, Mmax outside 0 .. 192; a NULL table
+ * or S <= 0; a NULL required operand; uniforms without teacher while sample_ratio > 0; an fp32 / int32 operand not 4-byte aligned or
+ * teacher not 8-byte aligned. */
+#define ETP_DECIDE_HDR 8
+#define ETP_DECIDE_STOP 1
+#define ETP_DECIDE_ERR_ACTION 2
+#define ETP_DECIDE_ERR_UNREACHABLE 4
+#define ETP_DECIDE_ERR_INPUT 8
+int etp_nav_decide(const float* logits, const float* node_pos, const int32_t* n_nodes, const float* adj, const float* ghost_pos,
+                   const int32_t* n_ghost, const int32_t* front_ptr, const int32_t* front_idx, const int32_t* cur_node,
+                   const int32_t* slot, const float* uniforms, const int64_t* teacher, float sample_ratio, int force_stop, int B,
+                   int Nmax, int Mmax, int Fmax, int G, float* stop_scores, int S, int32_t* record, etp_stream_t stream);
+
 /* Pre-training MLM task for a planner created with cfg.use_lang2visn = 1:
  * GlocalTextPathCMT.forward_mlm (pretrain vilmodel.py:708-754): the text (output of etp_txt_fwd) attends to the graph-node
  * inputs gmap_img_fts + step + position embeddings through forward_lang2visn of every x-layer (:400-411), then
