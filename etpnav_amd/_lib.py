@@ -90,7 +90,7 @@ class ProfEntry(ctypes.Structure):
 
 # ---- header parsing --------------------------------------------------------------------------
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
-            "float": ctypes.c_float,
+            "float": ctypes.c_float, "double": ctypes.c_double,
             "etp_stream_t": ctypes.c_void_p}
 
 

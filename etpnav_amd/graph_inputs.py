@@ -18,7 +18,10 @@ device tensors.
   **device-store mode** GraphMapLite is given ROW INDICES into one embedding store tensor instead of tensors
   (``update_graph(..., cur_embeds=row, cand_embeds=[rows])``); ``pack_img_csr`` turns the graphs into a CSR and
   ``gather_rows`` (autograd wrapper of ``etp_gather_sum``) produces the padded ``[B,G,H]`` tensor in one launch, with
-  the gradient flowing back into the store through the transposed CSR.
+  the gradient flowing back into the store through the transposed CSR;
+* ``DeviceGraphMaps`` keeps the maps themselves on the device (``etp_gmap_update``, csrc/gmap_update.hip): one launch per rollout
+  step maintains them in place and emits the compact arrays, ``etp_gmap_embed_csr`` builds the CSR there, and the host keeps a
+  ``GraphMapView`` of names and positions from a small record.  A route beside ``GraphMapLite`` + ``nav_gmap_variable``.
 
 ``cur_heading`` is the scalar heading (radians) that the reference obtains with ``heading_from_quaternion(cur_ori)``
 (graph_utils.py:54-59); quaternion handling belongs to the simulator side and is out of scope.
@@ -330,6 +333,286 @@ def gather_rows(store: torch.Tensor, gmaps: Sequence, row_offsets: Sequence[int]
     bwd = tuple(x.to(dev) for x in bwd)
     out = _GatherRows.apply(store.float().contiguous(), len(gmaps) * G, fwd, bwd)
     return out.view(len(gmaps), G, store.shape[1])
+
+
+# ---- the map itself on the device (csrc/gmap_update.hip): update_graph in one launch, nothing re-serialised --------------------
+GMAP_FMAX, GMAP_HDR, GMAP_KMAX = 512, 8, 16                   # ETP_GMAP_FMAX, ETP_GMAP_HDR, the kernel's candidate limit
+GMAP_ERR_CAPACITY, GMAP_ERR_INPUT, GMAP_ERR_ROW = 1, 2, 4     # ETP_GMAP_ERR_*
+GMAP_EDGE, GMAP_NEW, GMAP_MERGED = 1, 2, 3                    # ETP_GMAP_*: what became of a candidate (record, bits 24 ..)
+_NO_GPU = "the device-resident map (etp_gmap_update) needs an MI355X (cuda/hip device); no CPU fallback exists"
+
+
+class GraphMapView:
+    """What the host keeps of one environment's device-resident map: names and positions under the reference's attribute names
+    (graph_utils.py:143-161), filled from the kernel's record -- no distance is computed here.  ``RolloutDecider``,
+    ``env_actions_from_record`` and the trainer's ``_teacher_action_new`` read it like a GraphMapLite."""
+
+    def __init__(self, has_real_pos: bool):
+        self.has_real_pos = has_real_pos
+        self.node_pos: Dict[str, np.ndarray] = {}
+        self.node_stepId: Dict[str, int] = {}
+        self.ghost_cnt = 0
+        self.ghost_pos: Dict[str, list] = {}
+        self.ghost_mean_pos: Dict[str, np.ndarray] = {}
+        self.ghost_aug_pos: Dict[str, np.ndarray] = {}
+        self.ghost_fronts: Dict[str, list] = {}
+        self.ghost_real_pos: Dict[str, list] = {}
+        self.node_stop_scores: Dict[str, float] = {}
+        self._sum: Dict[str, np.ndarray] = {}
+        self.max_row = -1                                     # the largest row of the embedding store this map was ever given
+        self.pending_delete = -1                              # index, in the DEVICE's order, of the ghost the next update removes
+
+    def delete_ghost(self, vp: str) -> None:
+        """graph_utils.py:185-191 on the view; the device drops the ghost at the start of the next update (nothing reads the map
+        in between, ss_trainer_ETP.py:976-977)."""
+        if self.pending_delete >= 0:
+            raise ValueError("one ghost can be deleted between two updates (consume_ghost); a second delete_ghost is pending")
+        self.pending_delete = list(self.ghost_pos.keys()).index(vp)
+        for d in (self.ghost_pos, self.ghost_mean_pos, self.ghost_fronts, self._sum):
+            d.pop(vp)
+        self.ghost_aug_pos.pop(vp, None)
+        if self.has_real_pos:
+            self.ghost_real_pos.pop(vp)
+
+
+class DeviceGraphMaps:
+    """The maps of ``num_envs`` environments resident on the device, one state record per ORIGINAL environment, and a
+    ``GraphMapView`` of each on the host.
+
+        maps = DeviceGraphMaps(num_envs, device, has_real_pos, loc_noise, merge_ghost, ghost_aug)
+        cur_vp, cand_vp, cand_pos = maps.identify_node(cur_pos, cur_heading, cand_angles, cand_distances)
+        maps.update(prev_vp, step_ids, cur_vp, cur_pos, cur_heading, cand_pos, cur_rows, cand_rows, cand_real_pos)
+        nav_inputs = maps.nav_inputs()                        # the dict of nav_gmap_variable(..., keep_compact=True)
+        nav_inputs["gmap_img_fts"] = maps.img_fts(store, nav_inputs["gmap_masks"].shape[1])
+        ... decider.decide(nav_logits, maps.gmaps, cur_vp, ..., compact=nav_inputs.pop("compact")); maps.pause(i) beside decider.pause(i)
+
+    ``update`` is one host-to-device copy (every argument in one buffer), one launch of ``etp_gmap_update`` and ONE device-to-host
+    copy (the record).  What the kernel would flag (a full map, a ``prev_vp`` that is no node) is refused on the host before the launch,
+    so a ``ValueError`` leaves views and device records as they were."""
+
+    def __init__(self, num_envs: int, device, has_real_pos: bool, loc_noise: float, merge_ghost: bool, ghost_aug: float):
+        self.num_envs, self.device = int(num_envs), torch.device(device)
+        self.has_real_pos, self.loc_noise, self.merge_ghost, self.ghost_aug = bool(has_real_pos), float(loc_noise), bool(merge_ghost), float(ghost_aug)
+        self.state = None
+        self.out: Dict[str, torch.Tensor] = {}
+        if self.device.type == "cuda":
+            S, dev = self.num_envs, self.device
+            self.slot_bytes = int(_lib.lib().etp_gmap_slot_bytes())
+            self.state = torch.empty(S * self.slot_bytes, dtype=torch.uint8, device=dev)
+            f32, i32 = (lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)), (lambda *s: torch.empty(*s, dtype=torch.int32, device=dev))
+            self.out = {"node_pos": f32(S, MAX_NODES, 3), "node_step": i32(S, MAX_NODES), "n_nodes": i32(S), "adj": f32(S, MAX_NODES, MAX_NODES),
+                        "ghost_pos": f32(S, MAX_GHOSTS, 3), "n_ghost": i32(S), "front_ptr": i32(S, MAX_GHOSTS + 1), "front_idx": i32(S, GMAP_FMAX),
+                        "cur_node": i32(S), "cur_pos": f32(S, 3), "cur_heading": f32(S), "record": i32(S, GMAP_HDR + GMAP_KMAX)}
+        self.reset()
+
+    # ---- bookkeeping (RolloutDecider's) ----
+    def reset(self) -> None:
+        self.active = list(range(self.num_envs))
+        self.views = [GraphMapView(self.has_real_pos) for _ in range(self.num_envs)]
+        self.B = 0
+        self._slot_dev = None
+        if self.state is not None:
+            slots = torch.arange(self.num_envs, dtype=torch.int32).to(self.device)
+            check(_lib.lib().etp_gmap_reset(ptr(self.state), self.num_envs, ptr(slots), self.num_envs,
+                                            torch.cuda.current_stream(self.device).cuda_stream), "etp_gmap_reset")
+
+    def pause(self, i: int) -> None:
+        """``not_done_index.pop(i)`` (ss_trainer_ETP.py:1036-1044): the environment's record stays behind, untouched"""
+        self.active.pop(i)
+
+    @property
+    def gmaps(self) -> List[GraphMapView]:
+        return [self.views[s] for s in self.active]
+
+    def identify_node(self, cur_pos, cur_heading, cand_angles, cand_distances):
+        """GraphMap.identify_node (graph_utils.py:177-183, estimate_cand_pos :61-71) for every active environment -> (cur_vp [B],
+        cand_vp [B][K_b], cand_pos [B][K_b] arrays of 3).  A Python loop over the environments (K_b differs) with GraphMapLite's numpy
+        expressions on each, so the positions are its bits; it is not one vectorised call."""
+        cur_vp, cand_vp, cand_pos = [], [], []
+        for i, v in enumerate(self.gmaps):
+            vp = str(len(v.node_pos))
+            ang = (float(cur_heading[i]) + np.asarray(cand_angles[i], dtype=np.float64)) % (2 * np.pi)
+            dis = np.asarray(cand_distances[i], dtype=np.float64)
+            p = np.zeros((len(ang), 3))
+            p[:, 0] = cur_pos[i][0] - dis * np.sin(ang)
+            p[:, 1] = cur_pos[i][1]
+            p[:, 2] = cur_pos[i][2] - dis * np.cos(ang)
+            cur_vp.append(vp); cand_vp.append([f"{vp}_{k}" for k in range(len(ang))]); cand_pos.append([x for x in p])
+        return cur_vp, cand_vp, cand_pos
+
+    # ---- the update ----
+    def update(self, prev_vp, step_ids, cur_vp, cur_pos, cur_heading, cand_pos, cur_rows, cand_rows, cand_real_pos=None,
+               generator=None, noise=None) -> np.ndarray:
+        """GraphMap.update_graph for every active environment -> the record [B, 8 + 16] (include/etpnav_hip.h).  ``prev_vp[i]``: a
+        node's name or None; ``step_ids``: one int or [B]; ``cand_pos[i]`` / ``cand_rows[i]``: the K_i <= 16 candidates and their rows
+        of the embedding store; ``noise`` [B,192,3]: standard normals for ghost_aug (drawn from ``generator``, a numpy Generator,
+        when absent)."""
+        views, B, K = self.gmaps, len(self.active), GMAP_KMAX
+        if not (B and B == len(cur_vp) == len(prev_vp) == len(cand_pos) == len(cand_rows) == len(cur_rows)):
+            raise ValueError(f"{len(self.active)} active environments, {len(cur_vp)} viewpoints, {len(cand_pos)} candidate lists")
+        ks = [len(c) for c in cand_pos]
+        if max(ks) > K or any(len(r) != k for r, k in zip(cand_rows, ks)):
+            raise ValueError(f"at most {K} candidates per step, each with its row of the embedding store")
+        for v, vp in zip(views, cur_vp):
+            if vp != str(len(v.node_pos)):
+                raise ValueError(f"viewpoint {vp!r}: the next node of this map is {str(len(v.node_pos))!r} (identify_node)")
+        # what the kernel would flag is refused here, before the launch: a flagged episode would leave the other episodes' records
+        # advanced and no view mirrored.  The views hold the counts after the pending deletion.
+        for i, v in enumerate(views):
+            n, m, f = len(v.node_pos), len(v.ghost_pos), sum(len(x) for x in v.ghost_fronts.values())
+            if n + 1 > MAX_NODES or m + ks[i] > MAX_GHOSTS or f + ks[i] > GMAP_FMAX:
+                raise ValueError(f"episode {i}: the map is full (<= {MAX_NODES} visited nodes, {MAX_GHOSTS} ghosts, {GMAP_FMAX} absorbed candidates)")
+            if prev_vp[i] is not None and not (str(prev_vp[i]).isdigit() and int(prev_vp[i]) < n):
+                raise ValueError(f"episode {i}: prev_vp {prev_vp[i]!r} is no visited node of this map")
+            rows = [int(cur_rows[i])] + [int(r) for r in cand_rows[i]]
+            if min(rows) < 0:
+                raise ValueError(f"episode {i}: rows of the embedding store are >= 0")
+        if self.state is None:
+            raise _lib.EtpError(_NO_GPU)
+        for i, v in enumerate(views):
+            v.max_row = max([v.max_row, int(cur_rows[i])] + [int(r) for r in cand_rows[i]])
+        use_noise = self.ghost_aug != 0
+        if use_noise:
+            noise = (generator if generator is not None else np.random.default_rng()).standard_normal((B, MAX_GHOSTS, 3)) if noise is None \
+                else np.ascontiguousarray(noise, dtype=np.float64).reshape(B, MAX_GHOSTS, 3)
+        # one buffer, one copy: the doubles first, then the 4-byte operands
+        f64 = np.zeros(B * 3 + B * K * 3 + (B * MAX_GHOSTS * 3 if use_noise else 0))
+        i32 = np.zeros(B * (6 + K) + B, dtype=np.int32)
+        cp = f64[:B * 3].reshape(B, 3)
+        cq = f64[B * 3:B * 3 + B * K * 3].reshape(B, K, 3)
+        cp[:] = np.asarray(cur_pos, dtype=np.float64).reshape(B, 3)
+        if use_noise:
+            f64[B * 3 + B * K * 3:] = noise.ravel()
+        cols = i32[:B * 6].reshape(6, B)                      # slot, prev_node, step_id, n_cand, cur_row, del_ghost
+        crow = i32[B * 6:B * (6 + K)].reshape(B, K)
+        crow[:] = -1
+        cols[0], cols[2], cols[3], cols[4] = self.active, step_ids, ks, cur_rows
+        for i, v in enumerate(views):
+            cols[1, i] = -1 if prev_vp[i] is None else int(prev_vp[i])
+            cols[5, i] = v.pending_delete
+            if ks[i]:
+                cq[i, :ks[i]] = np.asarray(cand_pos[i], dtype=np.float64).reshape(ks[i], 3)
+                crow[i, :ks[i]] = cand_rows[i]
+        i32[B * (6 + K):].view(np.float32)[:] = np.asarray(cur_heading, dtype=np.float32).reshape(B)
+        host = np.concatenate([f64.view(np.uint8), i32.view(np.uint8)])
+        dev_buf = torch.from_numpy(host).to(self.device)
+        base = dev_buf.data_ptr()
+        o8, o4 = (lambda n: base + 8 * n), (lambda n: base + f64.nbytes + 4 * n)
+        o = self.out
+        check(_lib.lib().etp_gmap_update(
+            ptr(self.state), self.num_envs, o4(0), o4(B), o4(2 * B), o8(0), o4(B * (6 + K)), o8(B * 3), o4(3 * B), o4(4 * B), o4(6 * B), o4(5 * B),
+            o8(B * 3 + B * K * 3) if use_noise else None, self.loc_noise, int(self.merge_ghost), self.ghost_aug, B, K,
+            ptr(o["node_pos"]), ptr(o["node_step"]), ptr(o["n_nodes"]), ptr(o["adj"]), ptr(o["ghost_pos"]), ptr(o["n_ghost"]),
+            ptr(o["front_ptr"]), ptr(o["front_idx"]), ptr(o["cur_node"]), ptr(o["cur_pos"]), ptr(o["cur_heading"]), ptr(o["record"]),
+            torch.cuda.current_stream(self.device).cuda_stream), "etp_gmap_update")
+        self._slot_dev = dev_buf[f64.nbytes:f64.nbytes + 4 * B].view(torch.int32)
+        rec = o["record"][:B].cpu().numpy()                   # the one host synchronisation of the update
+        self.B = B
+        if rec[:, 2].any():                                  # refused above on the host; a flag here means view and record disagree
+            raise _lib.EtpError(f"etp_gmap_update flagged episodes {np.nonzero(rec[:, 2])[0].tolist()} (flags {rec[:, 2].tolist()}): "
+                                f"the views no longer describe the device records; reset()")
+        self._mirror(rec, views, cur_vp, cp, step_ids, cq, cand_real_pos, noise if use_noise else None)
+        return rec
+
+    def _mirror(self, rec, views, cur_vp, cur_pos, step_ids, cand_pos, cand_real_pos, noise) -> None:
+        """the views after the update, from the record alone: O(candidates) dictionary work per episode, no distances"""
+        steps = np.broadcast_to(np.asarray(step_ids), (len(views),))
+        scale = np.array([self.ghost_aug, 0.0, self.ghost_aug])
+        for i, v in enumerate(views):
+            v.pending_delete = -1
+            vp = cur_vp[i]
+            v.node_pos[vp], v.node_stepId[vp] = cur_pos[i].copy(), int(steps[i])
+            for k, c in enumerate(rec[i, GMAP_HDR:].tolist()):
+                if c < 0:
+                    break
+                kind, tgt = c >> 24, c & 0xFFFFFF
+                if kind == GMAP_EDGE:
+                    continue
+                gvp, pos = f"g{tgt}", cand_pos[i, k].copy()
+                real = cand_real_pos[i][k] if self.has_real_pos else None
+                if kind == GMAP_NEW:
+                    v.ghost_pos[gvp], v.ghost_mean_pos[gvp], v._sum[gvp], v.ghost_fronts[gvp] = [pos], pos, pos.copy(), [vp]
+                    if self.has_real_pos:
+                        v.ghost_real_pos[gvp] = [real]
+                else:
+                    v.ghost_pos[gvp].append(pos)
+                    v._sum[gvp] = v._sum[gvp] + pos
+                    v.ghost_mean_pos[gvp] = v._sum[gvp] / np.float64(len(v.ghost_pos[gvp]))
+                    v.ghost_fronts[gvp].append(vp)
+                    if self.has_real_pos:
+                        v.ghost_real_pos[gvp].append(real)
+            v.ghost_cnt = int(rec[i, 4])
+            if int(rec[i, 0]) != len(v.node_pos) or int(rec[i, 1]) != len(v.ghost_pos):
+                raise _lib.EtpError(f"episode {i}: the view holds {len(v.node_pos)} nodes / {len(v.ghost_pos)} ghosts, the device {rec[i, :2].tolist()}")
+            if noise is None or not v.ghost_mean_pos:
+                v.ghost_aug_pos = {k: np.array(p, dtype=np.float64) for k, p in v.ghost_mean_pos.items()}
+            else:
+                m = len(v.ghost_mean_pos)
+                aug = np.asarray(list(v.ghost_mean_pos.values())) + np.clip(noise[i, :m] * scale, -self.ghost_aug, self.ghost_aug)
+                v.ghost_aug_pos = dict(zip(v.ghost_mean_pos.keys(), aug))
+
+    # ---- the consumers' inputs ----
+    def compact(self) -> dict:
+        """the arrays the last update emitted, as ``assemble_on_device(..., keep_compact=True)`` returns them"""
+        if self.state is None or not self.B:
+            raise _lib.EtpError(_NO_GPU if self.state is None else "no update has run yet")
+        c = {k: v[:self.B] for k, v in self.out.items() if k != "record"}
+        c["_dims"] = (self.B, MAX_NODES, MAX_GHOSTS, GMAP_FMAX)
+        return c
+
+    def nav_inputs(self, G: Optional[int] = None) -> dict:
+        """the dict of ``nav_gmap_variable(..., keep_compact=True)`` (without gmap_img_fts: ``img_fts``) from the emitted arrays:
+        one launch of etp_gmap_assemble, nothing uploaded"""
+        t = self.compact()
+        views, B, dev = self.gmaps, self.B, self.device
+        need = max(1 + len(v.node_pos) + len(v.ghost_pos) for v in views)
+        G = need if G is None else G
+        if G < need:
+            raise ValueError(f"G={G} < 1 + nodes + ghosts = {need}")
+        out = {
+            "gmap_step_ids": torch.empty(B, G, dtype=torch.int64, device=dev),
+            "gmap_masks": torch.empty(B, G, dtype=torch.bool, device=dev),
+            "gmap_visited_masks": torch.empty(B, G, dtype=torch.bool, device=dev),
+            "gmap_pos_fts": torch.empty(B, G, 7, dtype=torch.float32, device=dev),
+            "gmap_pair_dists": torch.empty(B, G, G, dtype=torch.float32, device=dev),
+        }
+        check(_lib.lib().etp_gmap_assemble(ptr(t["node_pos"]), ptr(t["node_step"]), ptr(t["n_nodes"]), ptr(t["adj"]), ptr(t["ghost_pos"]),
+                                           ptr(t["n_ghost"]), ptr(t["front_ptr"]), ptr(t["front_idx"]), ptr(t["cur_node"]), ptr(t["cur_pos"]),
+                                           ptr(t["cur_heading"]), B, MAX_NODES, MAX_GHOSTS, GMAP_FMAX, G, ptr(out["gmap_step_ids"]),
+                                           ptr(out["gmap_masks"]), ptr(out["gmap_visited_masks"]), ptr(out["gmap_pos_fts"]),
+                                           ptr(out["gmap_pair_dists"]), torch.cuda.current_stream(dev).cuda_stream), "etp_gmap_assemble")
+        out["compact"] = t
+        out["gmap_vp_ids"] = [[None] + list(v.node_pos.keys()) + list(v.ghost_pos.keys()) for v in views]
+        out["no_vp_left"] = [len(v.ghost_pos) == 0 for v in views]
+        return out
+
+    def embed_csr(self, G: int, R: int):
+        """-> (ptr_f, idx_f, w_f), (ptr_b, idx_b, w_b), status on the device: ``pack_img_csr`` from the states (etp_gmap_embed_csr)"""
+        if self.state is None or not self.B:
+            raise _lib.EtpError(_NO_GPU if self.state is None else "no update has run yet")
+        views, B, dev = self.gmaps, self.B, self.device
+        need = max(1 + len(v.node_pos) + len(v.ghost_pos) for v in views)
+        if G < need:
+            raise ValueError(f"G={G} < 1 + nodes + ghosts = {need}")
+        nnz = max(1, sum(len(v.node_pos) + sum(len(f) for f in v.ghost_fronts.values()) for v in views))
+        i32, f32 = (lambda n: torch.empty(n, dtype=torch.int32, device=dev)), (lambda n: torch.empty(n, dtype=torch.float32, device=dev))
+        fwd, bwd, status = (i32(B * G + 1), i32(nnz), f32(nnz)), (i32(R + 1), i32(R), f32(R)), i32(B)
+        check(_lib.lib().etp_gmap_embed_csr(ptr(self.state), self.num_envs, ptr(self._slot_dev), B, G, R, ptr(fwd[0]), ptr(fwd[1]), ptr(fwd[2]),
+                                            ptr(bwd[0]), ptr(bwd[1]), ptr(bwd[2]), ptr(status), torch.cuda.current_stream(dev).cuda_stream),
+              "etp_gmap_embed_csr")
+        return fwd, bwd, status
+
+    def img_fts(self, store: torch.Tensor, G: int) -> torch.Tensor:
+        """gmap_img_fts [B,G,H] (fp32) from the embedding store [R,H]: ``gather_rows`` without the host-side CSR; differentiable
+        with respect to the store"""
+        if store.device.type != "cuda" or self.state is None:
+            raise _lib.EtpError(_NO_GPU)
+        top = max(v.max_row for v in self.gmaps)
+        if top >= store.shape[0]:                             # the kernel would flag it (ETP_GMAP_ERR_ROW) and gather row 0 with weight 0
+            raise ValueError(f"the maps hold row {top} of the embedding store, which has {store.shape[0]} rows")
+        fwd, bwd, _ = self.embed_csr(G, int(store.shape[0]))   # rows and G were checked on the host: the status is all zero
+        out = _GatherRows.apply(store.float().contiguous(), self.B * G, fwd, bwd)
+        return out.view(self.B, G, store.shape[1])
 
 
 # ---- panorama inputs: candidate views first, then the remaining panorama views (row a13, first half) -------------------

@@ -672,6 +672,72 @@ int etp_nav_decide(const float* logits, const float* node_pos, const int32_t* n_
                    const int32_t* slot, const float* uniforms, const int64_t* teacher, float sample_ratio, int force_stop, int B,
                    int Nmax, int Mmax, int Fmax, int G, float* stop_scores, int S, int32_t* record, etp_stream_t stream);
 
+/* The topological map on the device (csrc/gmap_update.hip): GraphMap.update_graph (vlnce_baselines/models/graph_utils.py:193-254)
+ * with _localize (:163-175) and delete_ghost (:185-191; consume_ghost, vlnce_baselines/ss_trainer_ETP.py:976-977) in one launch, on
+ * state that stays on the device.
+ * state: S records of etp_gmap_slot_bytes() bytes, 16-byte aligned, one per ORIGINAL environment (the convention of etp_nav_decide's
+ *   stop-score table); opaque apart from that stride.  A record holds <= 64 visited nodes, <= 192 ghosts and <= ETP_GMAP_FMAX absorbed
+ *   candidates; positions and the ghosts' running sums and means are double.  etp_gmap_reset empties the n given slots (a slot must be
+ *   reset before its first update; slots out of range are skipped).  A call never writes the record of a slot it was not given.
+ * etp_gmap_update, one workgroup per episode b (slots of one call must differ):
+ *   slot [B]; prev_node [B] (node index, -1: none); step_id [B]; cur_pos [B,3] f64; cur_heading [B] f32; cand_pos [B,Kmax,3] f64
+ *   (estimate_cand_pos, :61-71, stays on the host: sin / cos there keep numpy's bits); n_cand [B] in 0 .. Kmax; cur_row [B] and
+ *   cand_row [B,Kmax]: rows of the embedding store; del_ghost [B]: a ghost's index in the current order, or -1; noise [B,192,3] f64
+ *   standard normals or NULL; loc_noise, merge_ghost, ghost_aug: GraphMap's constructor arguments.
+ *   1. del_ghost >= 0: that ghost and everything it absorbed leave; the remaining ghosts keep their order.
+ *   2. the visited node is appended (index n): position, step_id, cur_row; edge prev_node - n of Euclidean length (:199-202).
+ *   3. every candidate in order (:208-246): the nearest visited node, the new one included (the FIRST minimum in insertion order, a
+ *      distance below 10000); if its distance is <= loc_noise the edge (n, that node) is set to the distance between the two NODES.
+ *      Otherwise, with merge_ghost, the nearest ghost MEAN by the same rule, the means as the previous candidate left them: the
+ *      candidate joins it (sum += position, mean = sum / count, front n and the row appended; duplicate fronts are kept).  Otherwise
+ *      a new ghost with id ghost_cnt++ at the end of the order.
+ *   4. ghost_aug_pos = mean + clip(noise * (aug, 0, aug), +-aug) for every ghost when ghost_aug != 0 and noise is given (:248-254:
+ *      the distribution of np.random.normal, not its stream), the mean otherwise.
+ *   5. outputs, in BATCH order, fp32 / int32, padded as graph_inputs.pack_batch pads them, with the FIXED strides Nmax = 64, Mmax = 192,
+ *      Fmax = ETP_GMAP_FMAX: node_pos [B,64,3], node_step [B,64], n_nodes [B], adj [B,64,64], ghost_pos [B,192,3] (the aug positions),
+ *      n_ghost [B], front_ptr [B,193], front_idx [B,ETP_GMAP_FMAX], cur_node [B] (= the new node), cur_pos [B,3], cur_heading [B]:
+ *      the operands of etp_gmap_assemble and etp_nav_decide.
+ *   6. record [B, ETP_GMAP_HDR + Kmax] int32: [0] nodes  [1] ghosts  [2] flags (ETP_GMAP_ERR_*)  [3] the new node  [4] ghost_cnt
+ *      [5] absorbed candidates held  [6] [7] 0;  then per candidate (kind << 24) | target: ETP_GMAP_EDGE with the node index,
+ *      ETP_GMAP_NEW / ETP_GMAP_MERGED with the ghost's id; -1 beyond n_cand.
+ *   Every operation on positions is one correctly rounded double operation in numpy's order (the file is compiled with contraction
+ *   off): (dx*dx + dy*dy) + dz*dz, one sqrt, sum / count.  Edge lengths are rounded to fp32 once, when they are set.
+ *   Before anything is changed, with n, m, f the slot's nodes, ghosts and absorbed candidates after the deletion: n + 1 > 64,
+ *   m + n_cand > 192 or f + n_cand > ETP_GMAP_FMAX (as if nothing merged) gives ETP_GMAP_ERR_CAPACITY; a slot outside 0 .. S-1, n_cand
+ *   outside 0 .. Kmax, prev_node outside -1 .. n-1, del_ghost outside -1 .. m-1 or a record whose counts are out of range gives
+ *   ETP_GMAP_ERR_INPUT.  Either way the slot's record stays as it was, the flags go to record[b,2] and the episode's outputs are
+ *   those of an empty map (n_nodes = n_ghost = 0).  Plain stores, no atomics: the same state and inputs give the same bits.
+ *   ETP_ERR_INVALID before anything is launched: a NULL operand (noise excepted), B <= 0, S <= 0, Kmax outside 1 .. 16, a state not
+ *   16-byte aligned, an fp64 operand not 8-byte or an fp32 / int32 operand not 4-byte aligned.
+ * etp_gmap_embed_csr: the CSR of graph_inputs.pack_img_csr from the states (get_node_embeds, graph_utils.py:272-276;
+ *   ss_trainer_ETP.py:360-365) in three launches, no atomics, no host synchronisation.  Forward, over the [B*G] padded entry list
+ *   ([stop], nodes, ghosts, padding): ptr_f [B*G+1], idx_f / w_f (room for the sum of nodes + absorbed candidates; at most
+ *   B * (64 + ETP_GMAP_FMAX)); a node is its row with weight 1, a ghost its absorbed rows in absorption order with weight 1/count.
+ *   Transposed, over the store rows 0 .. R-1: ptr_b [R+1], idx_b / w_b with room for R entries (a store row has at most one owner
+ *   among the episodes of the call; the owner map is built in idx_b / w_b and compacted in place).  status [B]: 0, or
+ *   ETP_GMAP_ERR_CAPACITY when G < 1 + nodes + ghosts, ETP_GMAP_ERR_INPUT for a slot out of range or a record whose counts are out of
+ *   range (never reset) -- either way the episode comes out empty and nothing of the record is indexed --,
+ *   ETP_GMAP_ERR_ROW when a stored row lies outside 0 .. R-1 (it is replaced by row 0 with weight 0).  ETP_ERR_INVALID before
+ *   anything is launched: a NULL or misaligned operand, B, S or R <= 0, G outside 1 .. 257. */
+#define ETP_GMAP_FMAX 512
+#define ETP_GMAP_HDR 8
+#define ETP_GMAP_ERR_CAPACITY 1
+#define ETP_GMAP_ERR_INPUT 2
+#define ETP_GMAP_ERR_ROW 4
+#define ETP_GMAP_EDGE 1
+#define ETP_GMAP_NEW 2
+#define ETP_GMAP_MERGED 3
+int64_t etp_gmap_slot_bytes(void);
+int etp_gmap_reset(void* state, int S, const int32_t* slots, int n, etp_stream_t stream);
+int etp_gmap_update(void* state, int S, const int32_t* slot, const int32_t* prev_node, const int32_t* step_id, const double* cur_pos,
+                    const float* cur_heading, const double* cand_pos, const int32_t* n_cand, const int32_t* cur_row,
+                    const int32_t* cand_row, const int32_t* del_ghost, const double* noise, double loc_noise, int merge_ghost,
+                    double ghost_aug, int B, int Kmax, float* node_pos, int32_t* node_step, int32_t* n_nodes, float* adj,
+                    float* ghost_pos, int32_t* n_ghost, int32_t* front_ptr, int32_t* front_idx, int32_t* cur_node, float* cur_pos_out,
+                    float* cur_heading_out, int32_t* record, etp_stream_t stream);
+int etp_gmap_embed_csr(const void* state, int S, const int32_t* slot, int B, int G, int R, int32_t* ptr_f, int32_t* idx_f, float* w_f,
+                       int32_t* ptr_b, int32_t* idx_b, float* w_b, int32_t* status, etp_stream_t stream);
+
 /* Pre-training MLM task for a planner created with cfg.use_lang2visn = 1:
  * GlocalTextPathCMT.forward_mlm (pretrain vilmodel.py:708-754): the text (output of etp_txt_fwd) attends to the graph-node
  * inputs gmap_img_fts + step + position embeddings through forward_lang2visn of every x-layer (:400-411), then
