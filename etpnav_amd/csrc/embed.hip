@@ -12,12 +12,9 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "row.h"
 
 namespace etp {
-
-template <int NCH> struct Row {  // per-lane slice of one H-wide row
-  float v[NCH][4];
-};
 
 template <int NCH> __device__ __forceinline__ float row_sum(const Row<NCH>& r) {
   float s = 0.f;
@@ -32,20 +29,6 @@ template <int NCH> __device__ __forceinline__ float row_dot(const Row<NCH>& a, c
 #pragma unroll
     for (int e = 0; e < 4; ++e) s += a.v[c][e] * b.v[c][e];
   return wave_sum(s);
-}
-template <int NCH, typename T> __device__ __forceinline__ void row_load(Row<NCH>& r, const T* p, int lane) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) load4(p + c * 256 + lane * 4, r.v[c]);
-}
-template <int NCH, typename T> __device__ __forceinline__ void row_store(const Row<NCH>& r, T* p, int lane) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) store4(p + c * 256 + lane * 4, r.v[c]);
-}
-template <int NCH> __device__ __forceinline__ void row_add(Row<NCH>& a, const Row<NCH>& b) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) a.v[c][e] += b.v[c][e];
 }
 // in place: x -> xhat = (x-mean)*rstd ; returns mean/rstd (two-pass variance, matches torch.nn.LayerNorm)
 template <int NCH> __device__ __forceinline__ void row_normalize(Row<NCH>& x, float eps, float& mean, float& rstd) {
@@ -92,12 +75,6 @@ template <int NCH> __device__ __forceinline__ void row_ln_bwd(Row<NCH>& d, const
 // Per-lane register accumulators for the parameter gradients that reduce over rows (dgamma = sum dy*xhat, ...).
 // Each wave accumulates over the rows it owns; block_flush then sums the block's 4 waves through a [4][H] LDS
 // scratch and issues ONE global atomic per column per block.  (LDS float atomics were measured 60x slower here.)
-template <int NCH> __device__ __forceinline__ void row_zero(Row<NCH>& a) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) a.v[c][e] = 0.f;
-}
 template <int NCH> __device__ __forceinline__ void acc_mul(Row<NCH>& acc, const Row<NCH>& a, const Row<NCH>& b) {
 #pragma unroll
   for (int c = 0; c < NCH; ++c)

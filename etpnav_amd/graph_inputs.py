@@ -23,6 +23,11 @@ device tensors.
   step maintains them in place and emits the compact arrays, ``etp_gmap_embed_csr`` builds the CSR there, and the host keeps a
   ``GraphMapView`` of names and positions from a small record.  A route beside ``GraphMapLite`` + ``nav_gmap_variable``.
 
+* ``EmbedStore`` builds the embedding store those rows live in (``etp_pano_store_fwd``, csrc/pano_store.hip): ``append`` turns the
+  panorama encoder's output of one rollout step into the step's rows (the masked panorama mean and the candidate views,
+  ss_trainer_ETP.py:838-839, 864-865) in one launch and hands back the row numbers ``update`` / ``update_graph`` take; the backward of
+  every later ``img_fts`` / ``gather_rows`` reaches the panorama encoder of the step that wrote a row.
+
 ``cur_heading`` is the scalar heading (radians) that the reference obtains with ``heading_from_quaternion(cur_ori)``
 (graph_utils.py:54-59); quaternion handling belongs to the simulator side and is out of scope.
 """
@@ -324,7 +329,10 @@ class _GatherRows(torch.autograd.Function):
 
 
 def gather_rows(store: torch.Tensor, gmaps: Sequence, row_offsets: Sequence[int], G: int) -> torch.Tensor:
-    """gmap_img_fts [B,G,H] (fp32) from the embedding store [R,H] on the device; differentiable w.r.t. the store."""
+    """gmap_img_fts [B,G,H] (fp32) from the embedding store [R,H] on the device; differentiable w.r.t. the store.  ``store``: a tensor,
+    or an ``EmbedStore`` (its rows used so far, differentiable w.r.t. the pano_embeds of every ``append``)."""
+    if isinstance(store, EmbedStore):
+        store = store.rows()
     if store.device.type != "cuda":
         raise _lib.EtpError("etp_gather_sum needs an MI355X (cuda/hip device); no CPU fallback exists")
     fwd, bwd = pack_img_csr(gmaps, row_offsets, G, store.shape[0])
@@ -340,6 +348,149 @@ GMAP_FMAX, GMAP_HDR, GMAP_KMAX = 512, 8, 16                   # ETP_GMAP_FMAX, E
 GMAP_ERR_CAPACITY, GMAP_ERR_INPUT, GMAP_ERR_ROW = 1, 2, 4     # ETP_GMAP_ERR_*
 GMAP_EDGE, GMAP_NEW, GMAP_MERGED = 1, 2, 3                    # ETP_GMAP_*: what became of a candidate (record, bits 24 ..)
 _NO_GPU = "the device-resident map (etp_gmap_update) needs an MI355X (cuda/hip device); no CPU fallback exists"
+
+
+# ---- the embedding store itself (csrc/pano_store.hip): panorama outputs to rows, one launch per step and direction ------------------
+PSTORE_ERR_EMPTY, PSTORE_ERR_MASKED, PSTORE_ERR_COUNT, PSTORE_ERR_ROW = 1, 2, 4, 8     # ETP_PSTORE_ERR_*
+PSTORE_VMAX = 64                                              # views per panorama the kernels take (one lane per view)
+
+
+def _alias_rows(buf: torch.Tensor, r0: int, n: int) -> torch.Tensor:
+    """rows r0 .. r0+n-1 of ``buf`` as a tensor of its own over the same memory: no view of ``buf`` in autograd's eyes, so the
+    kernels' writes into the buffer and ``reset`` never meet autograd's in-place bookkeeping"""
+    H = buf.shape[1]
+    return torch.empty(0, dtype=buf.dtype, device=buf.device).set_(buf.untyped_storage(), buf.storage_offset() + r0 * H, (n, H), (H, 1))
+
+
+class _PanoStoreFn(torch.autograd.Function):
+    """pano_embeds [B,V,H] -> the call's block of store rows (etp_pano_store_fwd writes them into the store's buffer); the backward is
+    etp_pano_store_bwd on the block's gradient with block-relative rows.  meta [3,B] int32: absolute base, n_cand, block-relative base."""
+
+    @staticmethod
+    def forward(ctx, pano_embeds, store, masks, nav_types, meta, status, r0, n_rows):
+        B, V, H = pano_embeds.shape
+        check(_lib.lib().etp_pano_store_fwd(ptr(pano_embeds), ptr(masks), ptr(nav_types), ptr(meta[0]), ptr(meta[1]), B, V, H, ptr(store.buf),
+                                            store.capacity, ptr(status), torch.cuda.current_stream(pano_embeds.device).cuda_stream),
+              "etp_pano_store_fwd")
+        ctx.save_for_backward(masks, nav_types, meta)
+        ctx.dims = (B, V, H, n_rows)
+        return _alias_rows(store.buf, r0, n_rows)
+
+    @staticmethod
+    def backward(ctx, d_block):
+        masks, nav_types, meta = ctx.saved_tensors
+        B, V, H, n_rows = ctx.dims
+        d_block = d_block.float().contiguous()
+        if d_block.data_ptr() % 16:
+            d_block = d_block.clone()
+        d_pano = torch.empty(B, V, H, dtype=torch.float32, device=d_block.device)
+        check(_lib.lib().etp_pano_store_bwd(ptr(d_block), ptr(masks), ptr(nav_types), ptr(meta[2]), ptr(meta[1]), B, V, H, n_rows, ptr(d_pano),
+                                            0, torch.cuda.current_stream(d_block.device).cuda_stream), "etp_pano_store_bwd")
+        return d_pano, None, None, None, None, None, None, None
+
+
+class _JoinBlocks(torch.autograd.Function):
+    """the blocks of every ``append`` so far -> the store's rows [R,H] as ONE tensor (they already lie behind one another in the
+    buffer: nothing is copied); the backward hands each block its slice of d_store, and autograd sums what every later step sent to
+    a block before that block's _PanoStoreFn.backward runs."""
+
+    @staticmethod
+    def forward(ctx, store, R, *blocks):
+        ctx.spans = store._spans[:len(blocks)]
+        return _alias_rows(store.buf, 0, R)
+
+    @staticmethod
+    def backward(ctx, d_store):
+        return (None, None) + tuple(d_store[r0:r0 + n] if need else None for (r0, n), need in zip(ctx.spans, ctx.needs_input_grad[2:]))
+
+
+class EmbedStore:
+    """The embedding store of one rollout: one fp32 [capacity_rows, hidden] buffer on the device whose rows ``DeviceGraphMaps.update``,
+    ``GraphMapLite.update_graph`` (device-store mode), ``DeviceGraphMaps.img_fts`` and ``gather_rows`` index.
+
+        store = EmbedStore(capacity_rows, hidden, device); store.reset()                     # once per rollout
+        cur_rows, cand_rows = store.append(pano_embeds, pano_masks, nav_types, n_cand)      # per step: ss_trainer_ETP.py:838-839, 864-865
+        maps.update(..., cur_rows, cand_rows); gmap_img_fts = maps.img_fts(store, G)
+        ... loss.backward(); store.check()
+
+    ``append`` gives episode b of the call ``1 + n_cand[b]`` consecutive rows behind the rows used so far, in episode order: the masked
+    panorama mean, then the views with ``nav_types == 1`` in view order.  It never synchronises: what the kernel flags (no unmasked view,
+    a candidate at a masked-out view, a candidate count other than ``n_cand[b]``) stays on the device until ``check()`` copies the
+    status vectors of all calls in one transfer and raises.  With autograd on, the gradient of every later ``img_fts`` / ``gather_rows``
+    flows through the rows into the ``pano_embeds`` of the call that wrote them; under ``torch.no_grad()`` no graph is built."""
+
+    def __init__(self, capacity_rows: int, hidden: int, device):
+        if hidden not in (256, 512, 768) or capacity_rows < 1:
+            raise ValueError(f"hidden is 256, 512 or 768 and capacity_rows positive (got {hidden}, {capacity_rows})")
+        self.capacity, self.hidden, self.device = int(capacity_rows), int(hidden), torch.device(device)
+        self.buf = torch.empty(self.capacity, self.hidden, dtype=torch.float32, device=self.device)
+        self.reset()
+
+    def reset(self) -> None:
+        self.buf.zero_()
+        self.rows_used = 0
+        self._blocks: List[torch.Tensor] = []                 # one per append, in row order
+        self._spans: List[tuple] = []                         # (first row, rows) of each
+        self._status: List[torch.Tensor] = []
+        self._checked = 0                                     # calls whose status check() has already seen
+
+    def append(self, pano_embeds: torch.Tensor, pano_masks: torch.Tensor, nav_types: torch.Tensor, n_cand: Sequence[int]):
+        """-> (cur_rows [B], cand_rows [B][n_cand[b]]) as Python ints.  ``pano_embeds`` [B,V,H] fp32, ``pano_masks`` [B,V] bool or uint8,
+        ``nav_types`` [B,V] int64, ``n_cand``: host list (``len(wp_outputs['cand_angles'][i])``).  ValueError before anything is launched,
+        the store unchanged: rows beyond the capacity, n_cand[b] outside 0 .. 16, V outside 1 .. 64, wrong shapes or dtypes."""
+        if not (torch.is_tensor(pano_embeds) and pano_embeds.dim() == 3 and pano_embeds.dtype == torch.float32 and pano_embeds.shape[2] == self.hidden):
+            raise ValueError(f"pano_embeds is a float32 tensor [B, V, {self.hidden}]")
+        B, V, H = pano_embeds.shape
+        if not (1 <= V <= PSTORE_VMAX and B >= 1):
+            raise ValueError(f"B >= 1 and 1 <= V <= {PSTORE_VMAX} views (got B={B}, V={V})")
+        if not (torch.is_tensor(pano_masks) and tuple(pano_masks.shape) == (B, V) and pano_masks.dtype in (torch.bool, torch.uint8)):
+            raise ValueError(f"pano_masks is a bool or uint8 tensor [{B}, {V}]")
+        if not (torch.is_tensor(nav_types) and tuple(nav_types.shape) == (B, V) and nav_types.dtype == torch.int64):
+            raise ValueError(f"nav_types is an int64 tensor [{B}, {V}]")
+        if any(t.device != self.buf.device for t in (pano_embeds, pano_masks, nav_types)):
+            raise ValueError(f"the store lives on {self.device}; so must pano_embeds, pano_masks and nav_types")
+        ks = [int(k) for k in n_cand]
+        if len(ks) != B or any(k < 0 or k > GMAP_KMAX for k in ks):
+            raise ValueError(f"n_cand holds one count in 0 .. {GMAP_KMAX} per episode (got {ks} for B={B})")
+        n_rows = B + sum(ks)
+        if self.rows_used + n_rows > self.capacity:
+            raise ValueError(f"{self.rows_used} rows used + {n_rows} new > capacity {self.capacity}")
+        if self.device.type != "cuda":
+            raise _lib.EtpError("the embedding store (etp_pano_store_fwd) needs an MI355X (cuda/hip device); no CPU fallback exists")
+        r0 = self.rows_used
+        rel = np.concatenate([[0], np.cumsum([1 + k for k in ks])[:-1]]).astype(np.int32)
+        meta = torch.from_numpy(np.stack([rel + r0, np.asarray(ks, dtype=np.int32), rel]).astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        masks = pano_masks.contiguous()
+        masks = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        block = _PanoStoreFn.apply(pano_embeds.contiguous(), self, masks, nav_types.contiguous(), meta, status, r0, n_rows)
+        self._blocks.append(block); self._spans.append((r0, n_rows)); self._status.append(status)
+        self.rows_used = r0 + n_rows
+        base = (rel + r0).tolist()
+        return base, [[base[b] + 1 + j for j in range(ks[b])] for b in range(B)]
+
+    def rows(self) -> torch.Tensor:
+        """the rows used so far, [rows_used, H], over the buffer's memory; with autograd on, differentiable with respect to the
+        pano_embeds of every append"""
+        R = self.rows_used
+        if torch.is_grad_enabled() and any(b.requires_grad for b in self._blocks):
+            return _JoinBlocks.apply(self, R, *self._blocks)
+        return self.buf[:R]
+
+    def check(self) -> None:
+        """one device-to-host copy of the status vectors of every append since the last check; raises naming call and episode"""
+        new = self._status[self._checked:]
+        if not new:
+            return
+        flags = torch.cat(new).cpu().numpy()
+        first, self._checked = self._checked, len(self._status)
+        if flags.any():
+            bad, o = [], 0
+            for c, s in enumerate(new):
+                bad += [f"call {first + c} episode {b}: flags {int(f)}" for b, f in enumerate(flags[o:o + len(s)]) if f]
+                o += len(s)
+            raise _lib.EtpError("etp_pano_store_fwd flagged (ETP_PSTORE_ERR_*: 1 no unmasked view, 2 candidate at a masked-out view, "
+                                "4 candidate count != n_cand, 8 rows outside the store): " + "; ".join(bad))
 
 
 class GraphMapView:
@@ -604,7 +755,10 @@ class DeviceGraphMaps:
 
     def img_fts(self, store: torch.Tensor, G: int) -> torch.Tensor:
         """gmap_img_fts [B,G,H] (fp32) from the embedding store [R,H]: ``gather_rows`` without the host-side CSR; differentiable
-        with respect to the store"""
+        with respect to the store.  ``store``: a tensor, or an ``EmbedStore`` (its rows used so far, differentiable with respect to the
+        pano_embeds of every ``append``)"""
+        if isinstance(store, EmbedStore):
+            store = store.rows()
         if store.device.type != "cuda" or self.state is None:
             raise _lib.EtpError(_NO_GPU)
         top = max(v.max_row for v in self.gmaps)

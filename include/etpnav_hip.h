@@ -738,6 +738,39 @@ int etp_gmap_update(void* state, int S, const int32_t* slot, const int32_t* prev
 int etp_gmap_embed_csr(const void* state, int S, const int32_t* slot, int B, int G, int R, int32_t* ptr_f, int32_t* idx_f, float* w_f,
                        int32_t* ptr_b, int32_t* idx_b, float* w_b, int32_t* status, etp_stream_t stream);
 
+/* The embedding store's rows from the panorama encoder's output (csrc/pano_store.hip): the masked panorama mean and the candidate
+ * selection of vlnce_baselines/ss_trainer_ETP.py:838-839, 864-869, laid down as the rows that GraphMap.update_graph keeps
+ * (vlnce_baselines/models/graph_utils.py:206,224,233) and that etp_gmap_update / etp_gmap_embed_csr / etp_gather_sum index.
+ * etp_pano_store_fwd, one launch: pano_embeds [B,V,H] fp32 (etp_pano_fwd's output), pano_masks [B,V] u8, nav_types [B,V] int64,
+ *   row_base [B] and n_cand [B] int32, store [R,H] fp32, status [B] int32.  For episode b
+ *     store[row_base[b]]          = (sum of the views with pano_masks != 0, added in VIEW ORDER in fp32) / their count: one true
+ *                                   division; views are selected by the mask, never multiplied by it, so a masked-out view may hold
+ *                                   anything;
+ *     store[row_base[b] + 1 + j]  = a bit copy of the j-th view with nav_types == 1, in view order (candidates need not come first).
+ *   Rows are relative to the `store` pointer given; no other row is written.  status[b] = 0, or the OR of ETP_PSTORE_ERR_EMPTY (no
+ *   unmasked view), ETP_PSTORE_ERR_MASKED (a candidate at a masked-out view), ETP_PSTORE_ERR_COUNT (the views with nav_types == 1
+ *   are not n_cand[b] many), ETP_PSTORE_ERR_ROW (row_base[b] < 0 or row_base[b] + 1 + candidates > R); a flagged episode writes
+ *   nothing to the store, and nothing is indexed by its values.  Episodes whose rows overlap are the caller's error.
+ * etp_pano_store_bwd, one launch: d_store [R,H] with the same masks, types, bases and counts (bases relative to the d_store pointer
+ *   given, so a block of the store's gradient goes with block-relative rows) ->
+ *     d_pano_embeds[b,v] = (pano_masks[b,v] ? d_store[row_base[b]] / count_b : 0) + (nav_types[b,v] == 1 ? d_store[row_base[b] + 1 +
+ *                          rank(v)] : 0), rank(v) = the candidates before view v; a candidate view receives both terms: the quotient
+ *                          is rounded, then the sum.
+ *   accumulate == 0: every element of d_pano_embeds is written, padded views and flagged episodes (the kernel derives the flags again;
+ *   it takes no status) with exact zeros.  accumulate == 1: the value is added to what is there; flagged episodes are left alone.
+ * Plain vector stores, no atomics, no scratch; the order of every sum is fixed by the data, so a second run gives the same bits.
+ * ETP_ERR_INVALID before anything is launched: H not 256 / 512 / 768, V outside 1 .. 64, B < 1, R < 1, accumulate not 0 / 1, a NULL
+ * operand, pano_embeds / store / d_store / d_pano_embeds not 16-byte aligned, nav_types not 8-byte or an int32 operand not 4-byte
+ * aligned. */
+#define ETP_PSTORE_ERR_EMPTY 1
+#define ETP_PSTORE_ERR_MASKED 2
+#define ETP_PSTORE_ERR_COUNT 4
+#define ETP_PSTORE_ERR_ROW 8
+int etp_pano_store_fwd(const float* pano_embeds, const uint8_t* pano_masks, const int64_t* nav_types, const int32_t* row_base,
+                       const int32_t* n_cand, int B, int V, int H, float* store, int R, int32_t* status, etp_stream_t stream);
+int etp_pano_store_bwd(const float* d_store, const uint8_t* pano_masks, const int64_t* nav_types, const int32_t* row_base,
+                       const int32_t* n_cand, int B, int V, int H, int R, float* d_pano_embeds, int accumulate, etp_stream_t stream);
+
 /* Pre-training MLM task for a planner created with cfg.use_lang2visn = 1:
  * GlocalTextPathCMT.forward_mlm (pretrain vilmodel.py:708-754): the text (output of etp_txt_fwd) attends to the graph-node
  * inputs gmap_img_fts + step + position embeddings through forward_lang2visn of every x-layer (:400-411), then
