@@ -484,6 +484,47 @@ int etp_scale_f32(float* p, int64_t n, float scale, etp_stream_t s) {
   ETP_REQUIRE(p, "null pointer");
   return scale_f32(p, n, scale, (hipStream_t)s);
 }
+int etp_vocab_ce(int dtype, const float* logits, const int64_t* labels, float* loss, void* dlogits, int Nm, int V, int ldv,
+                 float scale, etp_stream_t s) {
+  ETP_REQUIRE(dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
+  ETP_REQUIRE(logits && labels && loss && dlogits, "null pointer");
+  ETP_REQUIRE(Nm > 0 && V > 0 && ldv >= V, "Nm > 0, V > 0 and ldv >= V required");
+  return vocab_ce(dtype, logits, labels, loss, dlogits, Nm, V, ldv, scale, (hipStream_t)s);
+}
+int etp_gelu_bwd(int dtype, void* d, const void* z, int64_t n, etp_stream_t s) {
+  ETP_REQUIRE(dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
+  ETP_REQUIRE(d && z && n >= 0, "null pointer / negative count");
+  return gelu_bwd_inplace(dtype, d, z, (long)n, (hipStream_t)s);
+}
+int etp_sum_steps(int dtype, const void* src, void* dst, int64_t n, int steps, etp_stream_t s) {
+  ETP_REQUIRE(dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
+  ETP_REQUIRE(src && dst, "null pointer");
+  ETP_REQUIRE(n >= 0 && n % 4 == 0 && steps > 0, "n % 4 == 0 and steps > 0 required");
+  ETP_REQUIRE(((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "src / dst must be 16-byte aligned");
+  return sum_steps(dtype, src, dst, (long)n, steps, (hipStream_t)s);
+}
+int etp_repeat_block(const void* src, void* dst, int64_t bytes, int T, etp_stream_t s) {
+  ETP_REQUIRE(src && dst, "null pointer");
+  ETP_REQUIRE(bytes >= 0 && bytes % 16 == 0 && T >= 0, "bytes % 16 == 0 and T >= 0 required");
+  ETP_REQUIRE(((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "src / dst must be 16-byte aligned");
+  return repeat_block(src, dst, (long)bytes, T, (hipStream_t)s);
+}
+int etp_copy_f32(const float* src, float* dst, int64_t n, etp_stream_t s) {
+  ETP_REQUIRE(src && dst && n >= 0, "null pointer / negative count");
+  ETP_REQUIRE(((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "src / dst must be 16-byte aligned");
+  return copy_f32(src, dst, (long)n, (hipStream_t)s);
+}
+int etp_cast_f32_to(int dtype, const float* src, void* dst, int64_t n, etp_stream_t s) {
+  ETP_REQUIRE(dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
+  ETP_REQUIRE(src && dst, "null pointer");
+  ETP_REQUIRE(n >= 0 && n % 4 == 0, "n % 4 == 0 required");
+  ETP_REQUIRE(((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "src / dst must be 16-byte aligned");
+  return cast_drop(dtype, src, dst, (long)n, drop_none(), (hipStream_t)s);
+}
+int etp_seq_mask(const int64_t* lens, uint8_t* m1, uint8_t* m2, int B, int V, etp_stream_t s) {
+  ETP_REQUIRE(lens && m1, "null pointer");
+  return seq_mask(lens, m1, m2, B, V, (hipStream_t)s);
+}
 
 // ---- streams / graphs -----------------------------------------------------------------
 int etp_stream_create(etp_stream_t* out) {

@@ -1049,5 +1049,22 @@ int scale_f32(float* p, long n, float scale, hipStream_t st) {
   ETP_CHECK_LAUNCH("scale_f32");
   return ETP_OK;
 }
+// m1[b][v] = m2[b][v] = v < lens[b]  (gen_seq_masks common/ops.py:36-44); m2 may be NULL
+__global__ __launch_bounds__(256) void seq_mask_kernel(const int64_t* __restrict__ lens, uint8_t* __restrict__ m1,
+                                                       uint8_t* __restrict__ m2, int Bn, int V) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Bn * V) {
+    const uint8_t v = (i % V) < lens[i / V] ? 1 : 0;
+    m1[i] = v;
+    if (m2) m2[i] = v;
+  }
+}
+int seq_mask(const int64_t* lens, uint8_t* m1, uint8_t* m2, int B, int V, hipStream_t st) {
+  ETP_REQUIRE(B > 0 && V > 0, "bad dims");
+  const int M = B * V;
+  ETP_LAUNCH(seq_mask_kernel, dim3((M + 255) / 256), dim3(256), 0, st, lens, m1, m2, B, V);
+  ETP_CHECK_LAUNCH("seq_mask");
+  return ETP_OK;
+}
 
 }  // namespace etp

@@ -69,6 +69,7 @@ int gelu_bwd_inplace(int dtype, void* d, const void* z, long n, hipStream_t st);
 int zero_f32(float* dst, long n, hipStream_t st);
 int repeat_block(const void* src, void* dst, long bytes, int T, hipStream_t st);            // dst[t][.] = src[.], t < T
 int sum_steps(int dtype, const void* src, void* dst, long n, int steps, hipStream_t st);   // dst[i] = sum_t src[t][i], fp32 accumulation
+int seq_mask(const int64_t* lens, uint8_t* m1, uint8_t* m2, int B, int V, hipStream_t st);   // m[b][v] = v < lens[b]; m2 may be NULL
 
 // waypoint.hip: the waypoint predictor's neighbourhood attention and its heat-map tail (forward only)
 int ring_attn_fwd(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* ctx, long ldc, int B,

@@ -1122,15 +1122,6 @@ PanoStash plan_pano(const etp_planner* pl, Bump& b, int Bn, int V) {
   s.stn = (float*)b.take(M * 2 * sizeof(float));
   return s;
 }
-__global__ void seq_mask_kernel(const int64_t* __restrict__ lens, uint8_t* __restrict__ m1, uint8_t* __restrict__ m2, int Bn,
-                                int V) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < Bn * V) {
-    const uint8_t v = (i % V) < lens[i / V] ? 1 : 0;      // gen_seq_masks common/ops.py:36-44
-    m1[i] = v;
-    if (m2) m2[i] = v;
-  }
-}
 PanoEmbedParams pano_params(const etp_planner* p) {
   PanoEmbedParams q;
   q.g_img = p->pf(p->img_g); q.b_img = p->pf(p->img_bb);
@@ -1191,8 +1182,7 @@ int etp_pano_fwd(etp_planner* p, const float* rgb, const float* dep, const float
   const etp_config& cf = p->cfg;
   const int H = c.H, I = c.I, M = B * V;
   stamp_mark(c.st, 1100);
-  ETP_LAUNCH(seq_mask_kernel, dim3((M + 255) / 256), dim3(256), 0, c.st, view_lens, s.mask, out_mask, B, V);
-  ETP_CHECK_LAUNCH("seq_mask");
+  ETP_TRY(seq_mask(view_lens, s.mask, out_mask, B, V, c.st));
   const void* rgbT = rgb; const void* depT = dep;
   const Drop denv = site(c, p->p_env, MODE_PANO, 0, SITE_ENV);     // Policy_ViewSelection_ETP.py:102,345 (drop_env on the RGB features)
   if (c.dt == ETP_BF16 || denv.p > 0.f) {

@@ -343,6 +343,38 @@ int etp_cast_f32_to_bf16(const float* src, void* dst, int64_t n, etp_stream_t st
 int etp_cast_bf16_to_f32(const void* src, float* dst, int64_t n, float scale, etp_stream_t stream);
 int etp_scale_f32(float* p, int64_t n, float scale, etp_stream_t stream);
 
+/* Masked-LM loss over the vocabulary (pretrain_cmt.py:155-159: F.cross_entropy(reduction='none').mean() with scale = 1/Nm), one
+ * workgroup per masked token.  logits fp32 [Nm, ldv], ldv >= V; columns >= V are padding and are never read.  labels [Nm] in [0, V)
+ * (there is no ignore_index: the caller gathers the masked tokens).  dlogits [Nm, ldv] in `dtype` is OVERWRITTEN with
+ * scale * (softmax - onehot), one rounding to bf16 where dtype is ETP_BF16, and exactly 0 in the padding columns and in a -inf column
+ * no label points at.  *loss is ACCUMULATED (+= scale * nll of every row, one atomic per row: the order, and with it the last bits
+ * of the sum, may change from run to run); the caller zeroes it (etp_memset_async).  Refused: NULL pointers, Nm <= 0, V <= 0,
+ * ldv < V. */
+int etp_vocab_ce(int dtype, const float* logits, const int64_t* labels, float* loss, void* dlogits, int Nm, int V, int ldv,
+                 float scale, etp_stream_t stream);
+/* d[i] <- d[i] * gelu'(z[i]), gelu'(x) = Phi(x) + x phi(x) (erf form, BertPredictionHeadTransform's activation), in place; d and z in
+ * `dtype`, computed in fp32 with one rounding on the store; z is read only; scalar accesses, natural alignment, any n >= 0 (n = 0
+ * launches nothing).  x phi(x) is formed as written: z = +-inf gives NaN, as torch's own GELU backward does. */
+int etp_gelu_bwd(int dtype, void* d, const void* z, int64_t n, etp_stream_t stream);
+/* dst[i] = sum_{t < steps} src[t * n + i], accumulated in fp32 in the order t = 0, 1, ... and rounded once to `dtype` (steps = 1 is a
+ * bit-for-bit copy; the first addend is added onto +0).  Refused: NULL pointers, n % 4 != 0, steps <= 0, src or dst not 16-byte
+ * aligned.  n = 0 launches nothing. */
+int etp_sum_steps(int dtype, const void* src, void* dst, int64_t n, int steps, etp_stream_t stream);
+/* dst[t * bytes + i] = src[i] for t < T, byte for byte in 16-byte vectors (the text K|V cache replicated for T stacked steps); src and
+ * dst must not overlap.  Refused: NULL pointers, bytes % 16 != 0, src or dst not 16-byte aligned.  bytes = 0 or T = 0 launches
+ * nothing. */
+int etp_repeat_block(const void* src, void* dst, int64_t bytes, int T, etp_stream_t stream);
+/* dst[i] = src[i], i < n, bit for bit (float4 body, scalar tail of n % 4 elements); src == dst or n = 0 launches nothing; otherwise
+ * the buffers must not overlap.  Refused: NULL pointers, src or dst not 16-byte aligned. */
+int etp_copy_f32(const float* src, float* dst, int64_t n, etp_stream_t stream);
+/* dst[i] = (dtype) src[i]: fp32 -> the operand dtype in vectors of four (the panorama's RGB-feature conversion without its dropout).
+ * ETP_F32: a bit-for-bit copy; ETP_BF16: round-to-nearest-even, NaN stays NaN.  Refused: NULL pointers, n % 4 != 0, src or dst not
+ * 16-byte aligned.  n = 0 launches nothing. */
+int etp_cast_f32_to(int dtype, const float* src, void* dst, int64_t n, etp_stream_t stream);
+/* gen_seq_masks (common/ops.py:36-44): m1[b, v] = v < lens[b] ? 1 : 0 for b < B, v < V; m2 (nullable) receives the same bytes.  lens
+ * int64 [B]; a length <= 0 gives a row of zeros, a length >= V a row of ones.  Refused: NULL lens / m1, B <= 0, V <= 0. */
+int etp_seq_mask(const int64_t* lens, uint8_t* m1, uint8_t* m2, int B, int V, etp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused AdamW over flat fp32 arenas.  Replaces, in ONE HBM pass per step: torch.optim.AdamW
  * (ss_trainer_ETP.py:213,505) or the pre-training AdamW (pretrain_src/pretrain_src/optim/adamw.py:53-112),
@@ -621,7 +653,11 @@ int etp_gmap_assemble(const float* node_pos, const int32_t* node_step, const int
 /* RLTrainer._vp_feature_variable (ss_trainer_ETP.py:308-342): out[b] = [candidate-view features (K_b rows) ; panorama
  * views whose index is not a candidate's image, in index order], zero-padded to V rows; nav_types 1 for the candidate rows
  * (NULL to skip), view_lens[b] = K_b + #free views (NULL to skip).  cand_fts packed [sum K, F] with cand_ptr [B+1];
- * pano_fts [B,P,F] with pano_batch_stride = P*F, or one shared [P,F] table with stride 0 (pano_angle_fts); cand_mask [B,P]. */
+ * pano_fts [B,P,F] with pano_batch_stride = P*F, or one shared [P,F] table with stride 0 (pano_angle_fts); cand_mask [B,P]
+ * (non-zero = the view is a candidate's image).  cand_fts is not read, and may be NULL, when sum K = 0.
+ * PRECONDITION: V >= K_b + #free views for every episode (the caller sizes V from the batch maximum, graph_inputs.py).  With a
+ * smaller V nothing is written out of bounds, but the rows of the episode beyond V are dropped while view_lens[b] still reports the
+ * untruncated length: the outputs no longer describe each other, and no caller may rely on that case. */
 int etp_vp_gather(const float* cand_fts, const int32_t* cand_ptr, const float* pano_fts, int64_t pano_batch_stride,
                   const uint8_t* cand_mask, int B, int P, int F, int V, float* out_fts, int64_t* nav_types, int64_t* view_lens,
                   etp_stream_t stream);
@@ -856,6 +892,8 @@ int etp_rec_end(etp_graph** out, int64_t* n_kernels, int64_t* n_edges);
 int etp_rec_abort(void);
 int etp_graph_launch(etp_graph* g, etp_stream_t s);
 int etp_graph_destroy(etp_graph* g);
+/* memset of `bytes` bytes.  value == 0 with bytes % 4 == 0 and p 16-byte aligned: the library's own zeroing kernel (float4 body, scalar
+ * tail; recorded as a kernel node); everything else: the runtime's memset.  bytes = 0 does nothing. */
 int etp_memset_async(void* p, int value, int64_t bytes, etp_stream_t s);
 /* HIP-event timing on the given stream: elapsed ms of `iters` graph replays. */
 int etp_graph_time(etp_graph* g, etp_stream_t s, int iters, float* ms_out);

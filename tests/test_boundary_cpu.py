@@ -93,6 +93,20 @@ def test_argument_validation_without_launching():
     assert L.etp_ln_fwd(0, None, None, None, None, None, 4, 768, 1e-12, None) == -1
     cfg = _lib.Config()
     assert not L.etp_planner_create(ctypes.byref(cfg))
+    # the operator entry points of the MLM tail and the data-movement kernels refuse on the host (tests/test_move_kernels_gpu.py
+    # shows on the device that the outputs keep their fill)
+    x = torch.zeros(64)
+    y = torch.zeros(64)
+    lab = torch.zeros(4, dtype=torch.int64)
+    p, q = x.data_ptr(), y.data_ptr()
+    assert p % 16 == 0 and q % 16 == 0
+    refused = [L.etp_vocab_ce(0, None, lab.data_ptr(), q, q, 4, 8, 8, 1.0, None), L.etp_vocab_ce(0, p, lab.data_ptr(), q, q, 4, 9, 8, 1.0, None),
+               L.etp_gelu_bwd(0, None, p, 4, None), L.etp_sum_steps(0, p, q, 6, 2, None), L.etp_sum_steps(0, p, q, 8, 0, None),
+               L.etp_sum_steps(0, p + 4, q, 8, 2, None), L.etp_repeat_block(p, q, 40, 2, None), L.etp_repeat_block(p, q + 4, 32, 2, None),
+               L.etp_copy_f32(p + 4, q, 8, None), L.etp_copy_f32(p, None, 8, None), L.etp_cast_f32_to(1, p, q, 6, None),
+               L.etp_cast_f32_to(1, p, q + 8, 8, None), L.etp_seq_mask(None, q, None, 4, 8, None), L.etp_seq_mask(lab.data_ptr(), q, None, 0, 8, None)]
+    assert refused == [-1] * len(refused), refused
+    assert not bool(y.any())
 
 
 def test_policy_api_and_checkpoint_remap_cpu(tmp_path):
