@@ -46,10 +46,7 @@ constexpr int TQ = 128;
 constexpr int TP = 144;
 constexpr int PROJ_K = 768;                      // fused out-projection dgrad: the reduction (= hidden size of every planner the reference builds)
 constexpr int PROJ_SLAB_K = 128;                 // k-rows of W per slab, [128][64] bf16 = 16 KB
-constexpr int PROJ_RING = 3;                     // slabs resident (prefetch distance 2)
-#ifndef ETP_PROJ_FETCH_AT
-#define ETP_PROJ_FETCH_AT 2                      // Q / K / V global loads are issued this many slabs before the end of the prologue
-#endif
+constexpr int PROJ_RING = 3;                     // slabs resident (two in flight behind the one being read)
 __device__ __forceinline__ int tile_off(int row, int chunk) { return row * TQ + ((chunk ^ (row & 7)) << 4); }
 
 struct RowArgs {
@@ -97,32 +94,31 @@ __device__ __forceinline__ short4_t frag_t4(const char* tile, int row0, int col0
 }
 
 // global [rows_valid][64] (row stride ld) -> registers -> LDS natural tile [rows_pad][64], zero rows beyond rows_valid.  All
-// loads of all tiles are issued before the first LDS write (one round trip); the workgroup has >= 256 threads.
+// loads of all tiles are issued before the first LDS write (one round trip); the workgroup has >= 256 threads.  The fetch is
+// branch-free and unmasked on purpose: a load under a per-thread `if`, or a select right behind it, makes hipcc wait vmcnt(0) after
+// EVERY load (the ISA of the earlier form paid one full memory latency per 16-byte piece, 14 in a row for the backward's four
+// tiles); pieces past the tile re-read its last valid row (same cache lines) and the zeroing happens in the commit.
 template <int MAXROWS> struct TileRegs {
   static constexpr int N = (MAXROWS * 8 + 255) / 256;
   uint4 v[N];
 };
 template <int MAXROWS>
-__device__ __forceinline__ void tile_fetch(TileRegs<MAXROWS>& r, const bf16_t* __restrict__ g, long ld, int rows_valid, int rows_pad,
-                                           int tid, int nthr) {
+__device__ __forceinline__ void tile_fetch(TileRegs<MAXROWS>& r, const bf16_t* __restrict__ g, long ld, int rows_valid, int tid, int nthr) {
 #pragma unroll
   for (int j = 0; j < TileRegs<MAXROWS>::N; ++j) {
     const int q = tid + j * nthr, row = q >> 3, c = (q & 7) * 8;
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (row < rows_pad) {
-      const bool ok = row < rows_valid;
-      v = *reinterpret_cast<const uint4*>(g + (long)min(row, rows_valid - 1) * ld + c);
-      v.x = ok ? v.x : 0u; v.y = ok ? v.y : 0u; v.z = ok ? v.z : 0u; v.w = ok ? v.w : 0u;
-    }
-    r.v[j] = v;
+    r.v[j] = *reinterpret_cast<const uint4*>(g + (long)min(row, rows_valid - 1) * ld + c);
   }
 }
 template <int MAXROWS>
-__device__ __forceinline__ void tile_commit(char* lds, const TileRegs<MAXROWS>& r, int rows_pad, int tid, int nthr) {
+__device__ __forceinline__ void tile_commit(char* lds, const TileRegs<MAXROWS>& r, int rows_valid, int rows_pad, int tid, int nthr) {
 #pragma unroll
   for (int j = 0; j < TileRegs<MAXROWS>::N; ++j) {
     const int q = tid + j * nthr, row = q >> 3;
-    if (row < rows_pad) *reinterpret_cast<uint4*>(lds + tile_off(row, q & 7)) = r.v[j];
+    const bool ok = row < rows_valid;
+    uint4 v = r.v[j];
+    v.x = ok ? v.x : 0u; v.y = ok ? v.y : 0u; v.z = ok ? v.z : 0u; v.w = ok ? v.w : 0u;
+    if (row < rows_pad) *reinterpret_cast<uint4*>(lds + tile_off(row, q & 7)) = v;
   }
 }
 
@@ -147,35 +143,26 @@ __device__ __forceinline__ void store_rows16(char* strip, const f32x4_t (&acc)[4
 }
 
 // ---- pieces of the fused out-projection dgrad (rows_bwd_kernel<.., PROJ = true>) ----
-// one [128 k][64] slab of W (column block of this head) -> registers: 1024 16-byte pieces over the workgroup's threads
-template <int WN>
-__device__ __forceinline__ void proj_load_w(uint4 (&w)[WN], const bf16_t* __restrict__ Wg, long ldw, int s, int tid, int nthr) {
-#pragma unroll
-  for (int j = 0; j < WN; ++j) {
-    const int p = tid + j * nthr;
-    w[j] = make_uint4(0u, 0u, 0u, 0u);
-    if (p < PROJ_SLAB_K * 8) w[j] = *reinterpret_cast<const uint4*>(Wg + (long)(s * PROJ_SLAB_K + (p >> 3)) * ldw + (p & 7) * 8);
-  }
+// One LDS-DMA piece (1 KiB: lane l writes 16 bytes at lds_addr + 16 l) in SADDR form, as in gemm_mm32.hip: inline asm so that the
+// piece stays in flight until OUR counted s_waitcnt vmcnt + s_barrier retire it; M0 is written in the statement that consumes it
+// (tools/kernel_resources.py::m0_audit checks the ISA around every one of these after each build).
+__device__ __forceinline__ void proj_glds(unsigned voff, const char* sbase, unsigned lds_addr) {
+  asm volatile(
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %0, %1"
+      :
+      : "v"(voff), "s"(sbase), "s"(lds_addr)
+      : "memory");
 }
-// this lane's 8 consecutive k per k-step of its own dY row (B operand of the k=32 product), four steps per slab
-__device__ __forceinline__ void proj_load_y(uint4 (&y)[4], const bf16_t* __restrict__ Yr, int s, bool computing, bool qok) {
+template <int N> __device__ __forceinline__ void proj_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ void proj_wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// this lane's 8 consecutive k per k-step of its own dY row (B operand of the k=32 product), four steps per slab.  Branch-free and
+// unmasked on purpose: a load under an `if`, or a select right behind it, makes hipcc wait vmcnt(0) there, which would drain the DMA
+// ring; wavefronts without a query tile and rows past Lq read the last row (the tile's padded rows are zeroed where it is stored).
+__device__ __forceinline__ void proj_load_y(uint4 (&y)[4], const bf16_t* __restrict__ Yr, int s) {
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (computing) v = *reinterpret_cast<const uint4*>(Yr + s * PROJ_SLAB_K + 32 * u);
-    v.x = qok ? v.x : 0u; v.y = qok ? v.y : 0u; v.z = qok ? v.z : 0u; v.w = qok ? v.w : 0u;
-    y[u] = v;
-  }
-}
-// registers -> slab in LDS, rows permuted inside every 32: k = 8g+e -> row 4g+e (e < 4), 16+4g+(e-4) (e >= 4)
-template <int WN>
-__device__ __forceinline__ void proj_commit_w(char* slab, const uint4 (&w)[WN], int tid, int nthr) {
-#pragma unroll
-  for (int j = 0; j < WN; ++j) {
-    const int p = tid + j * nthr, kk = p >> 3;
-    const int row = (kk & ~0x1c) | ((kk & 0x4) << 2) | ((kk & 0x18) >> 1);
-    if (p < PROJ_SLAB_K * 8) *reinterpret_cast<uint4*>(slab + tile_off(row, p & 7)) = w[j];
-  }
+  for (int u = 0; u < 4; ++u) y[u] = *reinterpret_cast<const uint4*>(Yr + s * PROJ_SLAB_K + 32 * u);
 }
 
 // ---- pieces of the fused QKV projection (rows_fwd_kernel<.., QKV = true>) ----
@@ -253,14 +240,14 @@ __global__ __launch_bounds__(512) void rows_fwd_kernel(const RowArgs a) {
   const int bk = a.kv_mod > 0 ? b % a.kv_mod : b;
   if constexpr (!QKV) {
     TileRegs<BKV> rk, rv;
-    tile_fetch<BKV>(rk, a.K + (long)bk * a.Lk * a.ldk + h * 64, a.ldk, a.Lk, BKV, tid, nthr);
-    tile_fetch<BKV>(rv, a.V + (long)bk * a.Lk * a.ldv + h * 64, a.ldv, a.Lk, BKV, tid, nthr);
+    tile_fetch<BKV>(rk, a.K + (long)bk * a.Lk * a.ldk + h * 64, a.ldk, a.Lk, tid, nthr);
+    tile_fetch<BKV>(rv, a.V + (long)bk * a.Lk * a.ldv + h * 64, a.ldv, a.Lk, tid, nthr);
     // this wavefront's 16 queries go straight into the B-operand registers (rows past Lq repeat the last one; never stored)
     const bf16_t* Qr = a.Q + ((long)b * a.Lq + qc) * a.ldq + h * 64 + g * 8;
     qf0 = *reinterpret_cast<const uint4*>(Qr); qf1 = *reinterpret_cast<const uint4*>(Qr + 32);
     if (tid < BKV) kadd[tid] = key_term(a.keymask ? a.keymask + (long)bk * a.Lk : nullptr, tid, a.Lk, a.mask_mode);
-    tile_commit<BKV>(kt, rk, BKV, tid, nthr);
-    tile_commit<BKV>(vt, rv, BKV, tid, nthr);
+    tile_commit<BKV>(kt, rk, a.Lk, BKV, tid, nthr);
+    tile_commit<BKV>(vt, rv, a.Lk, BKV, tid, nthr);
   } else {
     constexpr int NS = PROJ_K / QKV_SLAB_K, WN = 6;                 // WN * 256 threads >= 1536 16-byte pieces of a slab
     const int Hh = a.nh * 64;
@@ -323,6 +310,18 @@ __global__ __launch_bounds__(512) void rows_fwd_kernel(const RowArgs a) {
   __syncthreads();
   if (wave * 16 >= a.Lq) return;               // helper wavefronts of a short query axis only staged K / V
 
+  float w = 0.f, b0 = 0.f;
+  // this lane's distances, all in flight at once behind the score products (branch-free: a load under `if (key < Lk)` is waited
+  // for with vmcnt(0), one full memory latency per element)
+  float dd[HAS_DIST ? NKT : 1][4];
+  if constexpr (HAS_DIST) {
+    w = a.sp_w[0]; b0 = a.sp_b[0];
+    const float* drow = a.dist + ((long)b * a.Lq + qc) * a.Lk;
+#pragma unroll
+    for (int n = 0; n < NKT; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dd[n][r] = drow[min(16 * n + 4 * g + r, a.Lk - 1)];
+  }
   f32x4_t s[NKT];
 #pragma unroll
   for (int n = 0; n < NKT; ++n) {
@@ -330,9 +329,6 @@ __global__ __launch_bounds__(512) void rows_fwd_kernel(const RowArgs a) {
     s[n] = mma32(frag(kt, 16 * n, 0, lane), qf0, s[n]);
     s[n] = mma32(frag(kt, 16 * n, 1, lane), qf1, s[n]);
   }
-  float w = 0.f, b0 = 0.f;
-  const float* drow = nullptr;
-  if constexpr (HAS_DIST) { w = a.sp_w[0]; b0 = a.sp_b[0]; drow = a.dist + ((long)b * a.Lq + qc) * a.Lk; }
   float mx = -INFINITY;
 #pragma unroll
   for (int n = 0; n < NKT; ++n) {
@@ -343,7 +339,8 @@ __global__ __launch_bounds__(512) void rows_fwd_kernel(const RowArgs a) {
       float v = s[n][r] * a.alpha + ka[r];
       if constexpr (HAS_DIST) {
         const int key = 16 * n + 4 * g + r;
-        if (key < a.Lk) v += w * drow[key] + b0;
+        const float vb = v + (w * dd[n][r] + b0);
+        v = key < a.Lk ? vb : v;
       }
       s[n][r] = v;
       mx = fmaxf(mx, v);
@@ -404,7 +401,7 @@ struct BwdLds {                                  // byte offsets for BQ = 16*cei
   }
 };
 
-// PROJ = true (round 6): the out-projection's input gradient (BertSelfOutput.dense, vilmodel_cmt.py:150-154; BertOutAttention /
+// PROJ = true: the out-projection's input gradient (BertSelfOutput.dense, vilmodel_cmt.py:150-154; BertOutAttention /
 // MHA out_proj alike) is no longer a GEMM launch of its own whose [B*Lq, H] result this kernel reads back as dO.  The workgroup of
 // (batch b, head h) computes its own 16*nqt x 64 tile  dO = dY[b rows, 0:Kp] . W[0:Kp, h*64 : h*64+64]  first:
 //   * dO^T = W_h^T dY^T with the k=32 MFMA: B operand = 8 consecutive k of the wavefront's OWN 16 rows of dY straight from global
@@ -412,11 +409,22 @@ struct BwdLds {                                  // byte offsets for BQ = 16*cei
 //     of a [128 k][64] slab in LDS by two ds_read_b64_tr_b16 -- the slab's rows are stored permuted (k = 8g+e -> row 4g+e, 16+4g+e-4
 //     within each 32) so that the two transposed reads of lane group g return exactly the 8 consecutive k its B operand holds and
 //     both reads keep frag_t4's conflict-free row pattern;
-//   * slabs travel global -> registers -> LDS two slabs ahead of their use (ring of 3 x 16 KB that ALIASES the Q / K / V tiles
-//     and the output strips, which are only needed afterwards; their global loads are in flight in registers meanwhile): the
-//     kernel's LDS footprint, and with it two workgroups per CU, is unchanged;
+//   * slabs travel global -> LDS by LDS-DMA (global_load_lds_dwordx4 in SADDR form, 16 one-KiB pieces per slab issued by wavefronts
+//     0..3, no register staging), two slabs in flight behind the one being read, in a ring of 3 x 16 KB that ALIASES the Q / K / V
+//     tiles and the output strips (only needed afterwards): the kernel's LDS footprint is unchanged.  The DMA writes lane-linear, so
+//     the row permutation and the chunk swizzle are applied to the SOURCE address.  Hand-over per slab: counted s_waitcnt vmcnt (the
+//     next slab and its dY landed, the one behind may stay in flight), lgkmcnt(0), raw s_barrier -- never __syncthreads(), whose
+//     fence would drain the ring.  Without the 32 staging registers every instantiation up to 80 keys needs <= 116 VGPRs (138 with the
+//     distance bias at 65..80 keys, whose plain kernel already takes 126), against 160..164 before: two five-wavefront workgroups
+//     co-reside on a CU whatever SIMDs the dispatcher picks;
+//   * Q / K / V are fetched behind the last hand-over (no DMA outstanding, so the compiler's own wait counts are exact again) and
+//     travel under the last slab's MFMAs.  They cannot come earlier without holding 40 registers through the prologue, and role A's
+//     score half cannot start before the ring is dead: its K tile lives where the ring is;
+//   * tried and removed: splitting the reduction over the wavefronts that own no query tile (partial tiles summed through LDS).  The
+//     prologue waits for slabs, not for MFMAs: graph -> text 16 x 80 at 384 workgroups 16.2 us with the split against 13.7 without,
+//     graph 16 x 16 12.6 against 10.6 (profiles/attn_fold_bench.txt);
 //   * the result lands in the dO tile as the same bf16 values the GEMM epilogue stored (round-to-nearest-even of the fp32 sum).
-// What it removes per attention block: one 128x64-class launch (9.9 us isolated for the text rows) + its boundary, 3.9 MB written
+// What it removes per attention block: one 128x64-class launch (8 us chained for the text rows) + its boundary, 3.9 MB written
 // and read back.
 template <int NKT, bool HAS_DIST, bool PROJ>
 __global__ __launch_bounds__(512) void rows_bwd_kernel(const RowArgs a) {
@@ -439,53 +447,84 @@ __global__ __launch_bounds__(512) void rows_bwd_kernel(const RowArgs a) {
     TileRegs<BKV> rk, rv;
     const int bk = a.kv_mod > 0 ? b % a.kv_mod : b;
 #define FETCH_QKV()                                                                                        \
-    tile_fetch<128>(rq, a.Q + (long)b * a.Lq * a.ldq + h * 64, a.ldq, a.Lq, BQ, tid, nthr);                 \
-    tile_fetch<BKV>(rk, a.K + (long)bk * a.Lk * a.ldk + h * 64, a.ldk, a.Lk, BKV, tid, nthr);               \
-    tile_fetch<BKV>(rv, a.V + (long)bk * a.Lk * a.ldv + h * 64, a.ldv, a.Lk, BKV, tid, nthr)
+    tile_fetch<128>(rq, a.Q + (long)b * a.Lq * a.ldq + h * 64, a.ldq, a.Lq, tid, nthr);                     \
+    tile_fetch<BKV>(rk, a.K + (long)bk * a.Lk * a.ldk + h * 64, a.ldk, a.Lk, tid, nthr);                    \
+    tile_fetch<BKV>(rv, a.V + (long)bk * a.Lk * a.ldv + h * 64, a.ldv, a.Lk, tid, nthr)
     if constexpr (!PROJ) {
       FETCH_QKV();
-      tile_fetch<128>(rd, a.dO + (long)b * a.Lq * a.ldd + h * 64, a.ldd, a.Lq, BQ, tid, nthr);
+      tile_fetch<128>(rd, a.dO + (long)b * a.Lq * a.ldd + h * 64, a.ldd, a.Lq, tid, nthr);
     } else {
-      constexpr int SLAB = PROJ_SLAB_K * TQ, WN = 4, NS = PROJ_K / PROJ_SLAB_K;     // WN * 256 threads >= 1024 16-byte pieces of a slab
+      constexpr int SLAB = PROJ_SLAB_K * TQ, NS = PROJ_K / PROJ_SLAB_K, NP = 4;     // NP 1-KiB DMA pieces per loader wavefront and slab
       char* ring = smem + L.ring;
-      const bf16_t* Wg = a.W + h * 64;
-      const int qrow = wave * 16 + i;
-      const bool computing = wave < nqt, qok = qrow < a.Lq;
+      const int wv = __builtin_amdgcn_readfirstlane(wave);
+      const bool computing = wv < nqt, loader = wv < 4;
+      const int qrow = wv * 16 + i;
+      const bool qok = qrow < a.Lq;
       const bf16_t* Yr = a.dO + ((long)b * a.Lq + min(qrow, a.Lq - 1)) * a.ldd + g * 8;
-      uint4 wr[2][WN], yb[3][4];
+      // DMA plan of the loader wavefronts 0..3: piece 4c + wv of a slab = its LDS rows 32c + 8wv .. +7, lane -> row R = .. + (lane >> 3),
+      // physical chunk lane & 7.  The DMA writes lane-linear, so both the row permutation (LDS row R holds k = the inverse of
+      // k = 8g+e -> row 4g+e | 16+4g+e-4, inside every 32) and the chunk swizzle go on the SOURCE address
+      const int r5 = 8 * (wv & 3) + (lane >> 3);
+      const int kk = (r5 & 3) | ((r5 & 0x10) >> 2) | ((r5 & 0xc) << 1);
+      const unsigned voff = (unsigned)(((long)kk * a.ldw + (((lane & 7) ^ (r5 & 7)) << 3)) * 2);
+      const char* wbase = reinterpret_cast<const char*>(a.W + h * 64);
+      const long piece_stride = 32 * a.ldw * 2, slab_stride = (long)PROJ_SLAB_K * a.ldw * 2;
+      const unsigned piece0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)ring) + (unsigned)(wv & 3) * 1024u;
+      auto issue_slab = [&](int s) {
+        if (loader) {
+#pragma unroll
+          for (int c = 0; c < NP; ++c) proj_glds(voff, wbase + s * slab_stride + c * piece_stride, piece0 + (unsigned)((s % PROJ_RING) * SLAB + c * 4096));
+        }
+      };
+      uint4 yb[2][4];
       f32x4_t acc[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-      proj_load_w<WN>(wr[0], Wg, a.ldw, 0, tid, nthr); proj_load_y(yb[0], Yr, 0, computing, qok);
-      proj_load_w<WN>(wr[1], Wg, a.ldw, 1, tid, nthr); proj_load_y(yb[1], Yr, 1, computing, qok);
-      proj_commit_w<WN>(ring, wr[0], tid, nthr);
-      __syncthreads();
+      // Order of the vector-memory issues (they retire in order, and the compiler does not count the DMA pieces): the dY loads of slab
+      // s+1 go out BEFORE the pieces of slab s+2 (those of slabs 0 and 1 before the whole ring), so that "at most the NP youngest
+      // outstanding" at a hand-over means slab s+1 and its dY both landed.
+      proj_load_y(yb[0], Yr, 0);
+      proj_load_y(yb[1], Yr, 1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < PROJ_RING; ++s) issue_slab(s);
+      __builtin_amdgcn_sched_barrier(0);
+      if (loader) proj_wait_vm<2 * NP>(); else proj_wait_vm<0>();
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        // slab s+2 -> registers (the set slab s was committed from); Q / K / V take the load slot once the last slab is on its way
-        if (s + 2 < NS) { proj_load_w<WN>(wr[s % 2], Wg, a.ldw, s + 2, tid, nthr); proj_load_y(yb[(s + 2) % 3], Yr, s + 2, computing, qok); }
-        if (s + ETP_PROJ_FETCH_AT == NS) { FETCH_QKV(); }
+        if (s >= 1 && s + 1 < NS) proj_load_y(yb[(s + 1) & 1], Yr, s + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        // slab s+2 into the slot slab s-1 left (every wavefront's reads of it retired at the hand-over just passed)
+        if (s >= 1 && s + 2 < NS) issue_slab(s + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        // Q / K / V take the load slot behind the last hand-over: no DMA is outstanding any more, the compiler's own counts are exact
+        if (s + 1 == NS) { FETCH_QKV(); }
         if (computing) {
-          const char* slab = ring + (s % 3) * SLAB;
+          const char* slab = ring + (s % PROJ_RING) * SLAB;
 #pragma unroll
           for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
               const short4_t lo = frag_t4(slab, 32 * u, 16 * t, lane), hi = frag_t4(slab, 32 * u + 16, 16 * t, lane);
               const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-              acc[t] = mma32(make_uint4(l2.x, l2.y, h2.x, h2.y), yb[s % 3][u], acc[t]);
+              acc[t] = mma32(make_uint4(l2.x, l2.y, h2.x, h2.y), yb[s & 1][u], acc[t]);
             }
         }
-        if (s + 1 < NS) {
-          proj_commit_w<WN>(ring + ((s + 1) % 3) * SLAB, wr[(s + 1) % 2], tid, nthr);
-          __syncthreads();
+        if (s + 1 < NS) {                           // hand-over: slab s+1 landed (slab s+2 may stay in flight), my reads of slab s retired
+          __builtin_amdgcn_sched_barrier(0);
+          if (loader && s + 2 < NS) proj_wait_vm<NP>(); else proj_wait_vm<0>();
+          proj_wait_lgkm0();
+          __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_sched_barrier(0);
         }
       }
       if (computing) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
-          *reinterpret_cast<uint2*>(dt + tile_off(16 * wave + i, 2 * t + (g >> 1)) + (g & 1) * 8) =
-              make_uint2(pack_bf16(acc[t][0], acc[t][1]), pack_bf16(acc[t][2], acc[t][3]));
+          *reinterpret_cast<uint2*>(dt + tile_off(16 * wv + i, 2 * t + (g >> 1)) + (g & 1) * 8) =
+              qok ? make_uint2(pack_bf16(acc[t][0], acc[t][1]), pack_bf16(acc[t][2], acc[t][3])) : make_uint2(0u, 0u);
       }
       __syncthreads();                            // the ring is dead: Q / K / V and the row vectors may land on it
     }
@@ -493,10 +532,10 @@ __global__ __launch_bounds__(512) void rows_bwd_kernel(const RowArgs a) {
     if (tid < BKV) kadd[tid] = key_term(a.keymask ? a.keymask + (long)bk * a.Lk : nullptr, tid, a.Lk, a.mask_mode);
     // padded query rows: lse = +inf makes their recomputed probabilities exactly 0
     if (tid < 128) lse[tid] = tid < a.Lq ? a.lse[(long)bh * a.Lq + tid] : INFINITY;
-    tile_commit<128>(qt, rq, BQ, tid, nthr);
-    if constexpr (!PROJ) tile_commit<128>(dt, rd, BQ, tid, nthr);
-    tile_commit<BKV>(kt, rk, BKV, tid, nthr);
-    tile_commit<BKV>(vt, rv, BKV, tid, nthr);
+    tile_commit<128>(qt, rq, a.Lq, BQ, tid, nthr);
+    if constexpr (!PROJ) tile_commit<128>(dt, rd, a.Lq, BQ, tid, nthr);
+    tile_commit<BKV>(kt, rk, a.Lk, BKV, tid, nthr);
+    tile_commit<BKV>(vt, rv, a.Lk, BKV, tid, nthr);
   }
   float w = 0.f, b0 = 0.f;
   if constexpr (HAS_DIST) { w = a.sp_w[0]; b0 = a.sp_b[0]; }
@@ -598,12 +637,18 @@ __global__ __launch_bounds__(512) void rows_bwd_kernel(const RowArgs a) {
       const float4 D4 = *reinterpret_cast<const float4*>(Dl + 16 * m + 4 * g);
       const float lr[4] = {l4.x, l4.y, l4.z, l4.w}, Dr[4] = {D4.x, D4.y, D4.z, D4.w};
       float pd[4], ds[4];
+      float dd[4] = {0.f, 0.f, 0.f, 0.f};         // the four distances of this step in flight together (branch-free, see rows_fwd_kernel)
+      if constexpr (HAS_DIST) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dd[r] = a.dist[((long)b * a.Lq + min(16 * m + 4 * g + r, a.Lq - 1)) * a.Lk + min(key, a.Lk - 1)];
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qq = 16 * m + 4 * g + r;
         float v = s[r] * a.alpha + ka;
         if constexpr (HAS_DIST) {
-          if (kok && qq < a.Lq) v += w * a.dist[((long)b * a.Lq + qq) * a.Lk + key] + b0;
+          const float vb = v + (w * dd[r] + b0);
+          v = (kok && qq < a.Lq) ? vb : v;
         }
         const float pe = __expf(v - lr[r]);
         float mult = 1.0f;

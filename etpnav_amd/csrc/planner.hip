@@ -558,13 +558,15 @@ int attn_bwd_impl(int dt, int nh, const AttnBuf& a, const void* P, const void* d
 }
 
 // When to fold a projection into the register-resident attention kernels (switches ATTN_PROJ / ATTN_QKV: 0 = never, 1 = always, unset =
-// the rule below).  Measured (profiles/r06_attn_fusion.txt): a fused prologue works on a smaller tile than the GEMM it replaces
-// (16*n x 64 rows x columns per workgroup against 128 x 64 / 128 x 128), i.e. it pulls more operand bytes per CU through the ~35 B/clk
-// L2 -> CU feed.
-//   * out-projection dgrad in the backward (96 KB of weights + the block's dY rows per workgroup): with ONE workgroup per CU
-//     (batch * heads <= CUs: configs 4 and 5, the SAP unit, rollout steps of <= 21 episodes) it wins about the launch it removes
-//     (config 5: -1.0 ... -1.4 % of the step); with two per CU (config 2: 384 workgroups of five wavefronts at 158 registers) the
-//     doubled feed costs more than the launch saved (text 80 x 80: 32.8 us against 22.2 us for the pair; step +1.7 %).  Rule: by grid.
+// the rule below).  Measured (profiles/attn_fold_bench.txt, attn_fold_ab_runs.json): a fused prologue works on a smaller tile than the
+// GEMM it replaces (16*n x 64 rows x columns per workgroup against 128 x 64 / 128 x 128), i.e. it pulls more operand bytes per CU through
+// the ~35 B/clk L2 -> CU feed.
+//   * out-projection dgrad in the backward (96 KB of weights by LDS-DMA + the block's dY rows per workgroup): alone it beats the launch
+//     pair wherever the query axis has four tiles or fewer (graph -> text 16 x 80 at 384 workgroups: 13.2 us against 14.0; panorama
+//     36 x 36: 13.3 against 15.0; graph 16 x 16: 10.7 against 12.4) and at one workgroup per CU (text 80 x 80, B = 16: 15.1 against
+//     17.5); the five-wavefront text shape at two workgroups per CU still loses (22.6 against 20.5 us: two workgroups of
+//     five query tiles share the CU's feed).  In the step (config 2, six alternating pairs): graph -> text folded 3.889 ms against 3.904 with the
+//     old rule, everything folded 3.908.  Rule: by grid, or by the query axis.
 //   * QKV projection in the forward (three times the weights: 288 KB + the block's rows per workgroup): slower than the launch pair at
 //     every grid size measured (B = 8: 17.4 against 14.2 us, B = 32: 33.6 against 24.0 us; config 5 step +1.4 %).  Rule: off.
 static bool fold_projection(Opt o, int workgroups, bool by_grid) {
@@ -574,18 +576,18 @@ static bool fold_projection(Opt o, int workgroups, bool by_grid) {
 }
 
 // Input gradient of an attention block's out-projection + the attention backward.  Where the register-resident kernels run (bf16, both
-// axes <= 128: every R2R-CE shape) AND the grid leaves every workgroup a CU of its own this is ONE launch -- the workgroup of a (batch,
-// head) computes its own dctx tile from dY and the projection's weight (attn_rows.hip, PROJ) -- otherwise the GEMM into `dctx` and the
-// attention backward reading it.
+// axes <= 128: every R2R-CE shape) AND the rule above says so this is ONE launch -- the workgroup of a (batch, head) computes its own
+// dctx tile from dY and the projection's weight (attn_rows.hip, PROJ) -- otherwise the GEMM into `dctx` and the attention backward
+// reading it.
 static int attn_bwd_proj(const Ctx& c, const AttnBuf& a, const void* P, const void* dy, int wi, void* dctx, int M, void* dP, void* dQ,
                          long lddq, void* dK, long lddk, void* dV, long lddv, float* d_sp_w, float* d_sp_b, Drop drop) {
   const int H = c.H;
   const void* W = c.pl->pw(wi);
   const int epc = 8;
-  // ... or four-wavefront workgroups (both axes <= 64: panorama 36 x 36, graph self-attention 16 x 16), which co-reside two per CU without
-  // the register-file lottery of the five-wavefront shapes: 15.8 against 16.9 us and 11.7 against 13.5 us at 384 workgroups
-  const bool four_waves = a.Lq <= 64 && a.Lk <= 64;
-  if (c.dt == ETP_BF16 && (fold_projection(OPT_ATTN_PROJ, a.B * c.nh, true) || (four_waves && fold_projection(OPT_ATTN_PROJ, 0, true))) &&
+  // ... or a query axis of at most four tiles (panorama 36 x 36, graph 16 x 16, graph -> text 16 x 80): at most four wavefronts run
+  // the projection MFMAs, and up to 80 keys these kernels need <= 118 registers (two workgroups always co-reside)
+  const bool few_query_tiles = a.Lq <= 64;
+  if (c.dt == ETP_BF16 && (fold_projection(OPT_ATTN_PROJ, a.B * c.nh, true) || (few_query_tiles && fold_projection(OPT_ATTN_PROJ, 0, true))) &&
       attn_rows_ok(c.dt, a, H) && attn_rows_proj_ok(H, W, H) &&
       lddq % epc == 0 && lddk % epc == 0 && lddv % epc == 0)
     return attn_rows_bwd(c.nh, a, P, dy, H, dQ, lddq, dK, lddk, dV, lddv, 0.125f, d_sp_w, d_sp_b, c.st, drop, W, H, H);
