@@ -79,6 +79,13 @@ int waypoint_tail(const float* logits, int B, int max_pred, float sigma_x, float
                   int32_t* cand_img_ccw, int32_t* samp_angle, int32_t* samp_dist, hipStream_t st);
 int waypoint_roll(const float* in, float* out, int B, hipStream_t st);     // out[b, a, d] = in[b, (a + 5) % 120, d]
 
+// clip.hip: the CLIP view encoder's own kernels (forward only; clip_engine.hip chains them with the GEMM / LayerNorm / attention launches)
+int clip_patch_rows(int dtype, const void* const* views, int n_views, int B, int S, void* out, hipStream_t st);
+int clip_tokens(const float* prod, const float* cls, const float* pos, const float* gamma, const float* beta, float* x, int N, int S,
+                float eps, hipStream_t st);
+int clip_cls_ln(int dtype, const float* x, const float* gamma, const float* beta, void* out, int N, int S, float eps, hipStream_t st);
+int quick_gelu_inplace(int dtype, void* x, long n, hipStream_t st);   // x = x * sigmoid(1.702 x); n % 8 == 0
+
 // optim.hip: fused AdamW (+ bf16 shadow refresh + gradient zeroing) and the gradient norm / non-finite scan
 int adamw_step(float* p, float* g, float* m, float* v, void* shadow, long n_shadow, const uint8_t* decay_mask, long n,
                const etp_adamw_cfg& c, const float* sumsq, const int32_t* skip, int zero_grads, hipStream_t st,

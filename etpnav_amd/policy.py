@@ -23,7 +23,8 @@ class ETP(nn.Module):
         # fused: the p=0.4 feature dropout rides in forward_panorama's operand cast (and its mask is recomputed for the
         # img_linear weight gradient and d rgb_fts) instead of a separate elementwise pass over [B,V,F] + a saved mask
         self.fuse_drop_env = fuse_drop_env
-        # mode='waypoint': the reference's VlnResnetDepthEncoder / CLIPEncoder (:118-138), supplied by the user; None = not attached
+        # mode='waypoint': the reference's VlnResnetDepthEncoder / CLIPEncoder (:118-138), supplied by the user (the rgb one may be
+        # etpnav_amd.clip.CLIPEncoder, the native view encoder); None = not attached
         self.depth_encoder = None
         self.rgb_encoder = None
         self.space_pool_depth = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), nn.Flatten(start_dim=2))   # :125

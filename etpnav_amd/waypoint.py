@@ -246,6 +246,8 @@ def waypoint_mode(net, waypoint_predictor, observations, in_train: bool, generat
     """Policy_ViewSelection_ETP.py:172-342 with the predictor and the heat-map tail on the device and ONE device-to-host copy (the
     candidate table) in place of the per-episode .nonzero() / .cpu() / .tolist() calls.  `net` supplies depth_encoder,
     rgb_encoder, space_pool_rgb, space_pool_depth, pano_angle_fts and pano_img_idxes."""
+    if hasattr(net.rgb_encoder, "encode_views"):
+        return _waypoint_mode_views(net, waypoint_predictor, observations, in_train, generator, uniforms)
     batch_size = observations["rgb"].shape[0]
     depth_batch = torch.zeros_like(observations["depth"]).repeat(NUM_IMGS, 1, 1, 1)
     rgb_batch = torch.zeros_like(observations["rgb"]).repeat(NUM_IMGS, 1, 1, 1)
@@ -260,7 +262,25 @@ def waypoint_mode(net, waypoint_predictor, observations, in_train: bool, generat
     obs_view12 = {"depth": depth_batch, "rgb": rgb_batch}
     depth_embedding = net.depth_encoder(obs_view12)       # [12B, 128, 4, 4]
     rgb_embedding = net.rgb_encoder(obs_view12)           # [12B, 512]
+    return _waypoint_tail_mode(net, waypoint_predictor, rgb_embedding, depth_embedding, batch_size, in_train, generator, uniforms)
 
+
+def _waypoint_mode_views(net, waypoint_predictor, observations, in_train, generator, uniforms):
+    """waypoint_mode with a native view encoder (etpnav_amd.clip.CLIPEncoder): the 12 rgb* tensors go to the encoder as they are -- its
+    patch kernel writes the clockwise order -- so only the depth half of the reorder (:182-190) is built here."""
+    batch_size = observations["rgb"].shape[0]
+    depth_batch = torch.zeros_like(observations["depth"]).repeat(NUM_IMGS, 1, 1, 1)
+    a_count = 0
+    for k, v in observations.items():
+        if "depth" in k:
+            depth_batch[(NUM_IMGS - a_count) % NUM_IMGS::NUM_IMGS] = v
+            a_count += 1
+    depth_embedding = net.depth_encoder({"depth": depth_batch})     # [12B, 128, 4, 4]
+    rgb_embedding = net.rgb_encoder.encode_views(observations)      # [12B, 512], clockwise
+    return _waypoint_tail_mode(net, waypoint_predictor, rgb_embedding, depth_embedding, batch_size, in_train, generator, uniforms)
+
+
+def _waypoint_tail_mode(net, waypoint_predictor, rgb_embedding, depth_embedding, batch_size, in_train, generator, uniforms):
     logits = waypoint_predictor(rgb_embedding, depth_embedding)
     cand = waypoint_predictor.candidates(logits, in_train, generator=generator, uniforms=uniforms)
     host = cand.table.cpu().numpy()                       # the one device-to-host copy of the call

@@ -535,6 +535,67 @@ int etp_waypoint_refresh_weights(etp_waypoint* w, etp_stream_t stream);
 int64_t etp_waypoint_ws_bytes(const etp_waypoint* w, int B);
 int etp_waypoint_fwd(etp_waypoint* w, const float* depth_feats, int B, float* logits, void* ws, etp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * CLIP ViT-B/32 view encoder: CLIPEncoder.forward (vlnce_baselines/models/encoders/resnet_encoders.py:244-278), the first GPU work of
+ * every rollout step (`rgb_embedding = self.rgb_encoder(obs_view12)`, Policy_ViewSelection_ETP.py:138,195).  Forward only: the encoder
+ * is frozen and in eval() (resnet_encoders.py:259-261).  S below is the image size: a multiple of 32 in 32 .. 224 (ViT-B/32: 224);
+ * T = (S / 32)^2 + 1 tokens per image.  Every entry point returns ETP_ERR_INVALID before anything is launched for a NULL pointer, a
+ * pointer not aligned to 16 bytes, S outside that set, or a non-positive image count.
+ * ---------------------------------------------------------------------------------------------------- */
+/* Replaces observations["rgb"].permute(0, 3, 1, 2), transforms.ConvertImageDtype(torch.float) and transforms.Normalize
+ * (resnet_encoders.py:264-267,274-275), the unfold of conv1 (clip/model.py VisionTransformer.forward: stride = kernel = 32) and -- with
+ * n_views == 12 -- the zero-filled rgb_batch and its 12 strided copies (Policy_ViewSelection_ETP.py:176-190).
+ * views: host array of n_views device pointers to uint8 tensors.  n_views == 1: one tensor [B, S, S, 3], image b -> slot b.
+ * n_views == 12: tensor a is view a of every episode, [B, S, S, 3]; view a of episode b -> slot (12 - a) % 12 + 12 b (clockwise order).
+ * out [n_views B (S/32)^2, 3072] in `dtype`: row = slot (S/32)^2 + patch (row-major), column = c 1024 + ky 32 + kx (conv1.weight's own
+ * order), value = (float(x) / 255 - mean[c]) / std[c] with each operation rounded in fp32 (bf16: then rounded to nearest even). */
+int etp_clip_patch_rows(int dtype, const void* const* views, int n_views, int B, int S, void* out, etp_stream_t stream);
+/* Replaces the class-token concatenation, `x + self.positional_embedding` and ln_pre (clip/model.py VisionTransformer.forward).
+ * prod [N (T-1), 768] fp32 = patch rows . conv1.weight^T; class_embedding [768]; pos [T, 768]; x [N T, 768] fp32 (eps 1e-5 in CLIP). */
+int etp_clip_tokens(const float* prod, const float* class_embedding, const float* pos, const float* gamma, const float* beta, float* x,
+                    int N, int S, float eps, etp_stream_t stream);
+/* Replaces QuickGELU (clip/model.py: x * torch.sigmoid(1.702 * x)) in place on n elements of `dtype`; n a positive multiple of 8.
+ * -inf gives NaN and +inf gives +inf, as torch does. */
+int etp_quick_gelu(int dtype, void* x, int64_t n, etp_stream_t stream);
+/* Replaces `self.ln_post(x[:, 0, :])` (clip/model.py VisionTransformer.forward): row 0 of every image of x [N T, 768] fp32 ->
+ * out [N, 768] in `dtype`. */
+int etp_clip_cls_ln(int dtype, const float* x, const float* gamma, const float* beta, void* out, int N, int S, float eps,
+                    etp_stream_t stream);
+
+typedef struct etp_clip_tensor_info {
+  char name[128];                        /* key of OpenAI CLIP's state dict without the leading "visual." */
+  int32_t ndim; int64_t shape[4];
+  int64_t offset;                        /* element offset in the fp32 arena (and, for the matrices, in the bf16 shadow) */
+} etp_clip_tensor_info;
+
+typedef struct etp_clip etp_clip;
+/* dtype ETP_F32 | ETP_BF16 (GEMM / attention operand precision; the residual stream and the LayerNorms are fp32 in both);
+ * image_size a multiple of 32 in 32 .. 224; layers 1 .. 12.  Width 768, 12 heads, patch 32, output 512 are fixed.  NULL on error. */
+etp_clip* etp_clip_create(int dtype, int image_size, int layers);
+void etp_clip_destroy(etp_clip* w);
+/* The parameter table: OpenAI CLIP's visual.* keys in the order of its state dict, with its shapes (152 tensors, 87 849 216 parameters
+ * at (224, 12)).  The GEMM matrices lead the arena ([0, etp_clip_matrix_elems)) and have a bf16 shadow at the same offsets; every
+ * offset is a multiple of 64 elements. */
+int etp_clip_param_count(const etp_clip* w);
+int etp_clip_param_info(const etp_clip* w, int i, etp_clip_tensor_info* out);
+int64_t etp_clip_arena_elems(const etp_clip* w);
+int64_t etp_clip_matrix_elems(const etp_clip* w);
+/* params: fp32 arena; shadow: bf16 copy of the matrix region (NULL in fp32 mode).  Both 256-byte aligned. */
+int etp_clip_bind(etp_clip* w, float* params, void* shadow);
+/* bf16 mode: shadow = bf16(params) over the matrix region (once after loading: the weights are frozen). */
+int etp_clip_refresh_weights(etp_clip* w, etp_stream_t stream);
+/* Replaces CLIPEncoder.forward (resnet_encoders.py:269-278 -> clip/model.py encode_image): views uint8 [N, S, S, 3] -> out [N, 512]
+ * fp32.  ws: etp_clip_ws_bytes(w, N) bytes of caller-owned scratch, 256-byte aligned (one plan for the whole call).
+ * 1 + 1 + 1 + 8 x layers + 2 launches, whatever N is. */
+int64_t etp_clip_ws_bytes(const etp_clip* w, int N);
+int etp_clip_fwd(etp_clip* w, const void* views, int N, float* out, void* ws, etp_stream_t stream);
+/* The same on the rollout's 12 view tensors (host array of 12 device pointers, each uint8 [B, S, S, 3]): replaces the rgb half of
+ * Policy_ViewSelection_ETP.py:176-195.  out [12 B, 512] in clockwise order; ws for N = 12 B. */
+int etp_clip_fwd_views(etp_clip* w, const void* const* views, int B, float* out, void* ws, etp_stream_t stream);
+/* Test aid: with a device buffer of 3 x N T x 768 fp32 installed, the following calls also copy the residual stream after ln_pre,
+ * after layer 0 and after the last layer into it (three more launches).  NULL removes it. */
+int etp_clip_set_probe(etp_clip* w, float* probe);
+
 /* Activations that cross these entry points (txt_embeds, pano_embeds, gmap_img_fts, gmap_embeds and their gradients) are
  * fp32 in BOTH modes, as they are under the reference's autocast (outputs of fp32 LayerNorms); `dtype` only selects the
  * GEMM / attention operand precision inside. */
