@@ -82,6 +82,11 @@ class ClipTensorInfo(ctypes.Structure):
                 ("offset", ctypes.c_int64)]
 
 
+class DepthTensorInfo(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 128), ("ndim", ctypes.c_int32), ("shape", ctypes.c_int64 * 4),
+                ("offset", ctypes.c_int64)]
+
+
 class AdamwCfg(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("weight_decay", ctypes.c_float), ("step", ctypes.c_int32), ("hf_style", ctypes.c_int32),

@@ -86,6 +86,16 @@ int clip_tokens(const float* prod, const float* cls, const float* pos, const flo
 int clip_cls_ln(int dtype, const float* x, const float* gamma, const float* beta, void* out, int N, int S, float eps, hipStream_t st);
 int quick_gelu_inplace(int dtype, void* x, long n, hipStream_t st);   // x = x * sigmoid(1.702 x); n % 8 == 0
 
+// depth.hip: the DD-PPO ResNet depth encoder's own kernels (forward only, NHWC; depth_engine.hip chains them with the GEMM launches)
+int depth_stem(const void* const* views, int n_views, int B, int S, int bp, const float* weight, float* out, hipStream_t st);
+int gn_stats(const float* x, float* stats, int N, int HW, int C, int G, float eps, hipStream_t st);   // stats [N, G, 2] = mean, rstd
+int gn_apply(int dtype, const float* x, const float* stats, const float* gamma, const float* beta, int res_kind, const void* res,
+             const float* stats2, const float* gamma2, const float* beta2, int relu, int nchw, void* out, int N, int HW, int C, int G,
+             hipStream_t st);
+int maxpool3x3s2(int dtype, const void* x, void* out, int N, int H, int W, int C, hipStream_t st);
+int conv_rows(int dtype, const void* x, void* out, int N, int H, int W, int C, int k, int stride, hipStream_t st);
+int depth_pack(int dtype, const float* src, void* dst, int Cout, int Cin, int kk, hipStream_t st);   // [Cout, Cin, kk] -> [Cout, kk, Cin]
+
 // optim.hip: fused AdamW (+ bf16 shadow refresh + gradient zeroing) and the gradient norm / non-finite scan
 int adamw_step(float* p, float* g, float* m, float* v, void* shadow, long n_shadow, const uint8_t* decay_mask, long n,
                const etp_adamw_cfg& c, const float* sumsq, const int32_t* skip, int zero_grads, hipStream_t st,

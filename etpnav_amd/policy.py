@@ -2,8 +2,10 @@
 
 ``ETP.forward(mode=...)`` keeps the reference's keyword names and dispatch (Policy_ViewSelection_ETP.py:157-170,
 :344-358) for the three planner modes.  ``mode='waypoint'`` (:172-342) runs the native waypoint head (etpnav_amd/waypoint.py)
-once the user has attached the reference's perception encoders as ``net.depth_encoder`` / ``net.rgb_encoder`` (habitat, CLIP
-and the DD-PPO ResNet stay out of scope); without them it raises NotImplementedError.
+once the two perception encoders are attached as ``net.depth_encoder`` / ``net.rgb_encoder``: the native ones
+(etpnav_amd.depth.DepthEncoder, the DD-PPO ResNet-50; etpnav_amd.clip.CLIPEncoder, the ViT-B/32), with which a rollout step
+needs neither habitat_baselines nor torch's convolution library, or the reference's own modules; without them it raises
+NotImplementedError (habitat's simulator itself stays out of scope).
 ``PolicyViewSelectionETP`` mirrors ILPolicy (models/policy.py:12-19): it just holds ``.net``.
 """
 from __future__ import annotations
@@ -23,8 +25,8 @@ class ETP(nn.Module):
         # fused: the p=0.4 feature dropout rides in forward_panorama's operand cast (and its mask is recomputed for the
         # img_linear weight gradient and d rgb_fts) instead of a separate elementwise pass over [B,V,F] + a saved mask
         self.fuse_drop_env = fuse_drop_env
-        # mode='waypoint': the reference's VlnResnetDepthEncoder / CLIPEncoder (:118-138), supplied by the user (the rgb one may be
-        # etpnav_amd.clip.CLIPEncoder, the native view encoder); None = not attached
+        # mode='waypoint': VlnResnetDepthEncoder / CLIPEncoder (:118-138), supplied by the user: the native etpnav_amd.depth.DepthEncoder
+        # and etpnav_amd.clip.CLIPEncoder, or the reference's modules; None = not attached
         self.depth_encoder = None
         self.rgb_encoder = None
         self.space_pool_depth = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), nn.Flatten(start_dim=2))   # :125
@@ -49,9 +51,9 @@ class ETP(nn.Module):
                                                     gmap_pos_fts, gmap_masks, gmap_visited_masks, gmap_pair_dists)
         if mode == "waypoint":
             if self.depth_encoder is None or self.rgb_encoder is None:
-                raise NotImplementedError("mode='waypoint' needs the reference's CLIP + DD-PPO encoders: attach them as "
-                                          "net.depth_encoder / net.rgb_encoder (INTEGRATION.md); this package replaces the "
-                                          "waypoint predictor and the heat-map tail behind them")
+                raise NotImplementedError("mode='waypoint' needs the CLIP + DD-PPO encoders: attach them as "
+                                          "net.depth_encoder / net.rgb_encoder (etpnav_amd.depth.DepthEncoder, "
+                                          "etpnav_amd.clip.CLIPEncoder or the reference's modules; INTEGRATION.md)")
             return waypoint_mode(self, waypoint_predictor, observations, in_train)
         raise NotImplementedError(mode)
 

@@ -246,7 +246,7 @@ def waypoint_mode(net, waypoint_predictor, observations, in_train: bool, generat
     """Policy_ViewSelection_ETP.py:172-342 with the predictor and the heat-map tail on the device and ONE device-to-host copy (the
     candidate table) in place of the per-episode .nonzero() / .cpu() / .tolist() calls.  `net` supplies depth_encoder,
     rgb_encoder, space_pool_rgb, space_pool_depth, pano_angle_fts and pano_img_idxes."""
-    if hasattr(net.rgb_encoder, "encode_views"):
+    if hasattr(net.rgb_encoder, "encode_views") or hasattr(net.depth_encoder, "encode_views"):
         return _waypoint_mode_views(net, waypoint_predictor, observations, in_train, generator, uniforms)
     batch_size = observations["rgb"].shape[0]
     depth_batch = torch.zeros_like(observations["depth"]).repeat(NUM_IMGS, 1, 1, 1)
@@ -266,17 +266,30 @@ def waypoint_mode(net, waypoint_predictor, observations, in_train: bool, generat
 
 
 def _waypoint_mode_views(net, waypoint_predictor, observations, in_train, generator, uniforms):
-    """waypoint_mode with a native view encoder (etpnav_amd.clip.CLIPEncoder): the 12 rgb* tensors go to the encoder as they are -- its
-    patch kernel writes the clockwise order -- so only the depth half of the reorder (:182-190) is built here."""
+    """waypoint_mode with a native view encoder on either side (etpnav_amd.clip.CLIPEncoder, etpnav_amd.depth.DepthEncoder): such an
+    encoder takes the 12 view tensors as they are -- its first kernel writes the clockwise order -- so only the other half of the reorder
+    (:182-190), if any, is built here.  The two sides are independent of each other."""
     batch_size = observations["rgb"].shape[0]
-    depth_batch = torch.zeros_like(observations["depth"]).repeat(NUM_IMGS, 1, 1, 1)
-    a_count = 0
-    for k, v in observations.items():
-        if "depth" in k:
-            depth_batch[(NUM_IMGS - a_count) % NUM_IMGS::NUM_IMGS] = v
-            a_count += 1
-    depth_embedding = net.depth_encoder({"depth": depth_batch})     # [12B, 128, 4, 4]
-    rgb_embedding = net.rgb_encoder.encode_views(observations)      # [12B, 512], clockwise
+    if hasattr(net.depth_encoder, "encode_views"):
+        depth_embedding = net.depth_encoder.encode_views(observations)  # [12B, 128, 4, 4], clockwise; no depth_batch
+    else:
+        depth_batch = torch.zeros_like(observations["depth"]).repeat(NUM_IMGS, 1, 1, 1)
+        a_count = 0
+        for k, v in observations.items():
+            if "depth" in k:
+                depth_batch[(NUM_IMGS - a_count) % NUM_IMGS::NUM_IMGS] = v
+                a_count += 1
+        depth_embedding = net.depth_encoder({"depth": depth_batch})     # [12B, 128, 4, 4]
+    if hasattr(net.rgb_encoder, "encode_views"):
+        rgb_embedding = net.rgb_encoder.encode_views(observations)      # [12B, 512], clockwise
+    else:
+        rgb_batch = torch.zeros_like(observations["rgb"]).repeat(NUM_IMGS, 1, 1, 1)
+        a_count = 0
+        for k in observations:
+            if "depth" in k:
+                rgb_batch[(NUM_IMGS - a_count) % NUM_IMGS::NUM_IMGS] = observations[k.replace("depth", "rgb")]
+                a_count += 1
+        rgb_embedding = net.rgb_encoder({"rgb": rgb_batch})             # [12B, 512]
     return _waypoint_tail_mode(net, waypoint_predictor, rgb_embedding, depth_embedding, batch_size, in_train, generator, uniforms)
 
 

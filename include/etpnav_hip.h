@@ -596,6 +596,80 @@ int etp_clip_fwd_views(etp_clip* w, const void* const* views, int B, float* out,
  * after layer 0 and after the last layer into it (three more launches).  NULL removes it. */
 int etp_clip_set_probe(etp_clip* w, float* probe);
 
+/* ------------------------------------------------------------------------------------------------------
+ * DD-PPO ResNet-50 depth encoder: VlnResnetDepthEncoder.forward (vlnce_baselines/models/encoders/resnet_encoders.py:13-107; habitat-lab
+ * rl/ddppo/policy/resnet.py and resnet_policy.py::ResNetEncoder with baseplanes 32, ngroups 16, no input normalisation,
+ * spatial_output False), `depth_embedding = self.depth_encoder(obs_view12)` of every rollout step (Policy_ViewSelection_ETP.py:194).
+ * Forward only: the encoder is frozen.  Activations are NHWC (a pixel's channels are contiguous).  Every entry point returns
+ * ETP_ERR_INVALID before anything is launched for a NULL pointer, a pointer not aligned to 16 bytes, a size outside its set, or a tensor of
+ * 2^31 elements or more.
+ * ---------------------------------------------------------------------------------------------------- */
+/* Replaces observations["depth"].permute(0, 3, 1, 2), F.avg_pool2d(x, 2) (resnet_policy.py ResNetEncoder.forward), backbone.conv1[0]
+ * (Conv2d(1, bp, 7, stride 2, pad 3, no bias)) and -- with n_views == 12 -- the zero-filled depth_batch and its 12 strided copies
+ * (Policy_ViewSelection_ETP.py:176-190).  views: host array of n_views device pointers to fp32 tensors.  n_views == 1: one tensor
+ * [B, S, S, 1], image b -> slot b.  n_views == 12: tensor a is view a of every episode; view a of episode b -> slot (12 - a) % 12 + 12 b.
+ * S a multiple of 64 in 64 .. 256, base_planes 16 | 32, weight [bp, 1, 7, 7] fp32, out [n_views B, S/4, S/4, bp] fp32 (pre-norm).
+ * Pooled pixel = ((a + b) + (c + d)) * 0.25 over its 2x2 block (rows first); output = the 49 taps in (ky, kx) order, one fused
+ * multiply-add each, zeros outside the pooled image. */
+int etp_depth_stem(const void* const* views, int n_views, int B, int S, int base_planes, const float* weight, float* out,
+                   etp_stream_t stream);
+/* GroupNorm statistics of x [N, HW, C] fp32 (groups of consecutive channels, biased variance): stats [N, groups, 2] = mean,
+ * 1 / sqrt(var + eps).  Two passes, the second around the mean; deterministic, no atomics.  C a multiple of 4, at most 2048; groups at
+ * most 64. */
+int etp_gn_stats(const float* x, float* stats, int N, int HW, int C, int groups, float eps, etp_stream_t stream);
+/* y = ((x - mean) * rstd) * gamma + beta in fp32, + residual (fp32), ReLU when relu != 0, rounded once.  res_kind 0: none; 1: res is a
+ * finished tensor [N, HW, C] in `dtype`; 2: res is a second pre-norm fp32 tensor normalised with stats2 / gamma2 / beta2 (the downsample
+ * branch of a bottleneck block).  nchw == 0: out [N, HW, C] in `dtype`; nchw != 0: out [N, C, HW] fp32. */
+int etp_gn_apply(int dtype, const float* x, const float* stats, const float* gamma, const float* beta, int res_kind, const void* res,
+                 const float* stats2, const float* gamma2, const float* beta2, int relu, int nchw, void* out, int N, int HW, int C,
+                 int groups, etp_stream_t stream);
+/* MaxPool2d(3, stride 2, pad 1) on x [N, H, W, C] in `dtype` -> out [N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C].  Padding is -inf: taps
+ * outside the image are skipped (equivalent to 0 behind a ReLU).  C a multiple of 8. */
+int etp_maxpool3x3s2(int dtype, const void* x, void* out, int N, int H, int W, int C, etp_stream_t stream);
+/* im2col: x [N, H, W, C] in `dtype` -> rows [N Ho Wo, k k C], column = (ky k + kx) C + c, zeros where the window leaves the image;
+ * k 1 | 3, stride 1 | 2, pad (k - 1) / 2, Ho = (H + 2 pad - k) / stride + 1.  k == 1 with stride 2 is the row gather of the strided
+ * downsample.  C a multiple of 8. */
+int etp_conv_rows(int dtype, const void* x, void* out, int N, int H, int W, int C, int k, int stride, etp_stream_t stream);
+
+typedef struct etp_depth_tensor_info {
+  char name[128];                        /* key of VlnResnetDepthEncoder.visual_encoder's state dict */
+  int32_t ndim; int64_t shape[4];
+  int64_t offset;                        /* element offset in the fp32 arena (and, for the matrices, in the packed copy) */
+} etp_depth_tensor_info;
+
+typedef struct etp_depth etp_depth;
+/* dtype ETP_F32 | ETP_BF16 (GEMM operand and activation precision; every product and every GroupNorm computes in fp32); image_size a
+ * multiple of 64 in 64 .. 256; base_planes 16 | 32 (groups = base_planes / 2); blocks[4] each 1 .. 6.  The shipped network is
+ * (256, 32, {3, 4, 6, 3}); the rest exists so that tests can be small.  Output channels Cc = round(2048 / (image_size / 64)^2).
+ * NULL on error. */
+etp_depth* etp_depth_create(int dtype, int image_size, int base_planes, const int* blocks);
+void etp_depth_destroy(etp_depth* w);
+/* The parameter table: the state dict's keys in its order, with its shapes (162 tensors, 7 069 408 parameters at the shipped size).  The
+ * GEMM matrices (every convolution but the stem's) lead the arena ([0, etp_depth_matrix_elems)); every offset is a multiple of 64. */
+int etp_depth_param_count(const etp_depth* w);
+int etp_depth_param_info(const etp_depth* w, int i, etp_depth_tensor_info* out);
+int64_t etp_depth_arena_elems(const etp_depth* w);
+int64_t etp_depth_matrix_elems(const etp_depth* w);
+int etp_depth_out_channels(const etp_depth* w);
+/* params: fp32 arena; packed: etp_depth_matrix_elems elements of `dtype`, the GEMM-ready copy (both modes).  Both 256-byte aligned. */
+int etp_depth_bind(etp_depth* w, float* params, void* packed);
+/* packed = the matrices in `dtype` at the arena's offsets, 3x3 weights permuted from [Cout, Cin, 3, 3] to [Cout, ky, kx, Cin], 1x1 weights
+ * as they are (one launch per matrix; needed once after loading: the weights are frozen). */
+int etp_depth_refresh_weights(etp_depth* w, etp_stream_t stream);
+/* Replaces VlnResnetDepthEncoder.forward (resnet_encoders.py:77-107): depth fp32 [N, S, S, 1] -> out [N, Cc, S/64, S/64] fp32, NCHW
+ * ([N, 128, 4, 4] at the shipped size).  ws: etp_depth_ws_bytes(w, N) bytes of caller-owned scratch, 256-byte aligned (one plan for the
+ * whole call, buffers reused across layers).  19 + 10 x (number of blocks) launches (179 at the shipped size), whatever N is; no
+ * allocation, no synchronisation. */
+int64_t etp_depth_ws_bytes(const etp_depth* w, int N);
+int etp_depth_fwd(etp_depth* w, const float* depth, int N, float* out, void* ws, etp_stream_t stream);
+/* The same on the rollout's 12 view tensors (host array of 12 device pointers, each fp32 [B, S, S, 1]): replaces the depth half of
+ * Policy_ViewSelection_ETP.py:176-194.  out [12 B, Cc, S/64, S/64] in clockwise order; ws for N = 12 B. */
+int etp_depth_fwd_views(etp_depth* w, const void* const* views, int B, float* out, void* ws, etp_stream_t stream);
+/* Test aid: with a device buffer installed, the following calls also copy (as fp32, NHWC, back to back) the activations after the
+ * max-pool [N, S/8, S/8, bp], after layer1 [N, S/8, S/8, 4 bp] and after layer4 [N, S/64, S/64, 32 bp] into it (three more launches).
+ * NULL removes it. */
+int etp_depth_set_probe(etp_depth* w, float* probe);
+
 /* Activations that cross these entry points (txt_embeds, pano_embeds, gmap_img_fts, gmap_embeds and their gradients) are
  * fp32 in BOTH modes, as they are under the reference's autocast (outputs of fp32 LayerNorms); `dtype` only selects the
  * GEMM / attention operand precision inside. */
