@@ -63,6 +63,12 @@ class AttnBwdDesc(ctypes.Structure):
                 ("d_sp_w", ctypes.c_void_p), ("d_sp_b", ctypes.c_void_p)]
 
 
+class DropSite(ctypes.Structure):
+    """etp_drop_site: one dropout site for the `_drop` entry points (pass ``ctypes.byref(site)`` or None)."""
+    _fields_ = [("p", ctypes.c_float), ("seed", ctypes.c_uint64), ("mode", ctypes.c_int32), ("layer", ctypes.c_int32),
+                ("slot", ctypes.c_int32)]
+
+
 class Config(ctypes.Structure):
     _fields_ = [("hidden", ctypes.c_int32), ("heads", ctypes.c_int32), ("inter", ctypes.c_int32),
                 ("n_l", ctypes.c_int32), ("n_p", ctypes.c_int32), ("n_x", ctypes.c_int32),

@@ -192,6 +192,21 @@ void stamp_mark(hipStream_t st, int tag) {
 template <typename... P> static bool aligned16(P... p) { return ((... | (uintptr_t)p) % 16) == 0; }
 template <typename... P> static bool aligned_rows(int dtype, P... p) { return ((... | (uintptr_t)p) % (dtype == ETP_BF16 ? 8 : 16)) == 0; }
 
+// ETP_REQUIRE under the name of the public entry point an internal body serves (the plain call and its _drop twin share one body)
+#define ETP_REQUIRE_AS(who, cond, msg)                                                      \
+  do {                                                                                      \
+    if (!(cond)) return ::etp::fail(ETP_ERR_INVALID, std::string(who) + ": " + (msg));      \
+  } while (0)
+// etp_drop_site -> Drop; NULL or p == 0 is drop_none().  The checks of etp_dropout_multipliers.
+static int site_to_drop(const char* who, const etp_drop_site* s, Drop& d) {
+  d = drop_none();
+  if (s == nullptr) return ETP_OK;
+  ETP_REQUIRE_AS(who, s->p >= 0.f && s->p < 1.f && s->mode >= 0 && s->layer >= 0 && s->slot >= 0 && s->slot < 16,
+                 "dropout site: p in [0, 1), mode >= 0, layer >= 0, 0 <= slot < 16 required");
+  if (s->p > 0.f) d = drop_site(s->p, s->seed, (uint32_t)(s->mode << 16 | s->layer << 4 | s->slot));
+  return ETP_OK;
+}
+
 extern "C" {
 
 const char* etp_version(void) { return "etpnav_hip 0.1.0 (gfx950)"; }
@@ -219,11 +234,14 @@ static int desc_to_args(const etp_gemm_desc* d, GemmArgs& g) {
   g.a_colsum = d->a_colsum;
   return ETP_OK;
 }
-int etp_gemm(const etp_gemm_desc* d, etp_stream_t stream) {
+// (a mask on a split or batched product is refused by the launcher: prepare_args in gemm.hip)
+int etp_gemm_drop(const etp_gemm_desc* d, etp_stream_t stream, const etp_drop_site* drop) {
   GemmArgs g;
   ETP_TRY(desc_to_args(d, g));
+  ETP_TRY(site_to_drop(__func__, drop, g.drop));
   return launch_gemm(d->dtype, d->c_dtype, d->trans_a, d->trans_b, g, d->batch > 0 ? d->batch : 1, (hipStream_t)stream);
 }
+int etp_gemm(const etp_gemm_desc* d, etp_stream_t stream) { return etp_gemm_drop(d, stream, nullptr); }
 // descriptors of a group -> gs, with etp_gemm_group's checks (shared with etp_gemm_instance: the same refusals, word for word)
 static int group_to_args(const etp_gemm_desc* d, int n, GemmArgs* gs) {
   if (!(d && n >= 1 && n <= ETP_GEMM_GROUP_MAX)) return fail(ETP_ERR_INVALID, "etp_gemm_group: 1..8 descriptors");
@@ -270,18 +288,41 @@ int etp_ln_stream_fwd(int dtype, const float* x, const float* gamma, const float
   ETP_REQUIRE(aligned16(x, gamma, beta, y) && aligned_rows(dtype, y_lp), "x / gamma / beta / y must be 16-byte aligned, y_lp to four elements");
   return ln_fwd_s(dtype, x, gamma, beta, y, y_lp, stats, M, H, eps, (hipStream_t)s);
 }
+static int ln_stream_bwd_body(const char* who, int dtype, const float* dy, const float* x, const float* stats, const float* gamma,
+                              const float* add, float* dx, void* dx_lp, float* dgamma, float* dbeta, int M, int H, etp_stream_t s,
+                              const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, dy && x && stats && gamma && (dx || dx_lp) && ((dgamma == nullptr) == (dbeta == nullptr)), "null pointer");
+  ETP_REQUIRE_AS(who, aligned16(dy, x, gamma, add, dx) && aligned_rows(dtype, dx_lp), "dy / x / gamma / add / dx must be 16-byte aligned, dx_lp to four elements");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  return ln_bwd_s(dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, M, H, (hipStream_t)s, drop);
+}
+int etp_ln_stream_bwd_drop(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add,
+                           float* dx, void* dx_lp, float* dgamma, float* dbeta, int M, int H, etp_stream_t s, const etp_drop_site* drop) {
+  return ln_stream_bwd_body(__func__, dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, M, H, s, drop);
+}
 int etp_ln_stream_bwd(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add,
                       float* dx, void* dx_lp, float* dgamma, float* dbeta, int M, int H, etp_stream_t s) {
-  ETP_REQUIRE(dy && x && stats && gamma && (dx || dx_lp) && ((dgamma == nullptr) == (dbeta == nullptr)), "null pointer");
-  ETP_REQUIRE(aligned16(dy, x, gamma, add, dx) && aligned_rows(dtype, dx_lp), "dy / x / gamma / add / dx must be 16-byte aligned, dx_lp to four elements");
-  return ln_bwd_s(dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, M, H, (hipStream_t)s);
+  return ln_stream_bwd_body(__func__, dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, M, H, s, nullptr);
 }
 int64_t etp_ln_bwd_part_bytes(int M, int H) { return (M > 0 && H > 0) ? (int64_t)ln_bwd_part_bytes(M, H) : 0; }
+static int ln_stream_bwd_stage1_body(const char* who, int dtype, const float* dy, const float* x, const float* stats,
+                                     const float* gamma, const float* add, float* dx, void* dx_lp, float* dgamma, float* dbeta,
+                                     float* part, int M, int H, etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, dy && x && stats && gamma && (dx || dx_lp) && dgamma && dbeta && part, "null pointer");
+  ETP_REQUIRE_AS(who, aligned16(dy, x, gamma, add, dx) && aligned_rows(dtype, dx_lp), "dy / x / gamma / add / dx must be 16-byte aligned, dx_lp to four elements");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  return ln_bwd_s(dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, M, H, (hipStream_t)s, drop, part);
+}
+int etp_ln_stream_bwd_stage1_drop(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add,
+                                  float* dx, void* dx_lp, float* dgamma, float* dbeta, float* part, int M, int H, etp_stream_t s,
+                                  const etp_drop_site* drop) {
+  return ln_stream_bwd_stage1_body(__func__, dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, part, M, H, s, drop);
+}
 int etp_ln_stream_bwd_stage1(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add,
                              float* dx, void* dx_lp, float* dgamma, float* dbeta, float* part, int M, int H, etp_stream_t s) {
-  ETP_REQUIRE(dy && x && stats && gamma && (dx || dx_lp) && dgamma && dbeta && part, "null pointer");
-  ETP_REQUIRE(aligned16(dy, x, gamma, add, dx) && aligned_rows(dtype, dx_lp), "dy / x / gamma / add / dx must be 16-byte aligned, dx_lp to four elements");
-  return ln_bwd_s(dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, M, H, (hipStream_t)s, drop_none(), part);
+  return ln_stream_bwd_stage1_body(__func__, dtype, dy, x, stats, gamma, add, dx, dx_lp, dgamma, dbeta, part, M, H, s, nullptr);
 }
 int etp_ln_part_reduce(const float* part, int M, int H, float* dgamma, float* dbeta, etp_stream_t s) {
   return ln_part_reduce(part, M, H, dgamma, dbeta, (hipStream_t)s);
@@ -301,23 +342,39 @@ static AttnBuf to_buf(const etp_attn_desc& f) {
   AttnBuf a{f.Q, f.ldq, f.K, f.ldk, f.V, f.ldv, f.B, f.Lq, f.Lk, f.ldS, f.keymask, f.mask_mode, f.dist, f.sp_w, f.sp_b};
   return a;
 }
-int etp_attn_fwd(const etp_attn_desc* d, etp_stream_t s) {
-  ETP_REQUIRE(d && d->Q && d->K && d->V && d->P && d->ctx, "null pointer");
-  ETP_REQUIRE(d->ldS >= d->Lk && d->ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
-  return attn_fwd_impl(d->dtype, d->heads, to_buf(*d), d->P, d->ctx, d->ldc, d->alpha, (hipStream_t)s);
+// Pd: the second [B, heads, Lq, ldS] probability buffer of the batched-GEMM family (AttnBuf::Pd); the other families ignore it
+static int attn_fwd_body(const char* who, const etp_attn_desc* d, etp_stream_t s, void* Pd, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, d && d->Q && d->K && d->V && d->P && d->ctx, "null pointer");
+  ETP_REQUIRE_AS(who, d->ldS >= d->Lk && d->ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  AttnBuf ab = to_buf(*d);
+  ab.Pd = Pd;
+  return attn_fwd_impl(d->dtype, d->heads, ab, d->P, d->ctx, d->ldc, d->alpha, (hipStream_t)s, drop);
 }
+int etp_attn_fwd_drop(const etp_attn_desc* d, etp_stream_t s, void* Pd, const etp_drop_site* drop) {
+  return attn_fwd_body(__func__, d, s, Pd, drop);
+}
+int etp_attn_fwd(const etp_attn_desc* d, etp_stream_t s) { return attn_fwd_body(__func__, d, s, nullptr, nullptr); }
 int etp_attn_family(const etp_attn_desc* d) {
   ETP_REQUIRE(d && d->Q && d->K && d->V, "null pointer");
   return attn_family(d->dtype, to_buf(*d), d->ldc);
 }
-int etp_attn_bwd(const etp_attn_bwd_desc* d, etp_stream_t s) {
-  ETP_REQUIRE(d && d->f.Q && d->f.K && d->f.V && d->f.P && d->dctx && d->dP && d->dQ && d->dK && d->dV, "null pointer");
-  ETP_REQUIRE(d->f.ldS >= d->f.Lk && d->f.ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+static int attn_bwd_body(const char* who, const etp_attn_bwd_desc* d, etp_stream_t s, void* Pd, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, d && d->f.Q && d->f.K && d->f.V && d->f.P && d->dctx && d->dP && d->dQ && d->dK && d->dV, "null pointer");
+  ETP_REQUIRE_AS(who, d->f.ldS >= d->f.Lk && d->f.ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
   AttnBuf ab = to_buf(d->f);
+  ab.Pd = Pd;
   ab.O = d->f.ctx; ab.ldo = d->f.ldc;          // the forward output (the streaming kernels need it)
   return attn_bwd_impl(d->f.dtype, d->f.heads, ab, d->f.P, d->dctx, d->ldd, d->dP, d->dQ, d->lddq, d->dK, d->lddk,
-                       d->dV, d->lddv, d->f.alpha, d->d_sp_w, d->d_sp_b, (hipStream_t)s);
+                       d->dV, d->lddv, d->f.alpha, d->d_sp_w, d->d_sp_b, (hipStream_t)s, drop);
 }
+int etp_attn_bwd_drop(const etp_attn_bwd_desc* d, etp_stream_t s, void* Pd, const etp_drop_site* drop) {
+  return attn_bwd_body(__func__, d, s, Pd, drop);
+}
+int etp_attn_bwd(const etp_attn_bwd_desc* d, etp_stream_t s) { return attn_bwd_body(__func__, d, s, nullptr, nullptr); }
 
 // per-episode K/V indirection at operator level: the families whose kernels carry kv_mod (2 register-resident, 3 streaming)
 static int kv_family(const char* who, const etp_attn_desc& f, int kv_mod, int sum_steps, AttnBuf& ab) {
@@ -353,58 +410,123 @@ int etp_attn_bwd_kv(const etp_attn_bwd_desc* d, int kv_mod, int sum_steps, etp_s
                        d->dV, d->lddv, d->f.alpha, d->d_sp_w, d->d_sp_b, (hipStream_t)s);
 }
 
-int etp_attn_fwd_qkv(const etp_attn_desc* d, const void* x, int64_t ldx, const void* w_qkv, int64_t ldw, const float* b_qkv, etp_stream_t s) {
-  ETP_REQUIRE(d && d->Q && d->K && d->V && d->P && d->ctx && x && w_qkv, "null pointer");
-  ETP_REQUIRE(d->ldS >= d->Lk && d->ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+static int attn_fwd_qkv_body(const char* who, const etp_attn_desc* d, const void* x, int64_t ldx, const void* w_qkv, int64_t ldw,
+                             const float* b_qkv, etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, d && d->Q && d->K && d->V && d->P && d->ctx && x && w_qkv, "null pointer");
+  ETP_REQUIRE_AS(who, d->ldS >= d->Lk && d->ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
   const AttnBuf ab = to_buf(*d);
   if (!(d->dtype == ETP_BF16 && attn_rows_ok(d->dtype, ab, d->ldc) && attn_rows_qkv_ok(d->heads, ab, x, ldx, w_qkv, ldw))) {
-    set_error("etp_attn_fwd_qkv: shape / dtype outside the fused kernel (bf16 self-attention, L <= 128, heads*64 == 768)");
+    set_error(std::string(who) + ": shape / dtype outside the fused kernel (bf16 self-attention, L <= 128, heads*64 == 768)");
     return ETP_ERR_INVALID;
   }
-  return attn_rows_fwd(d->heads, ab, d->P, d->ctx, d->ldc, d->alpha, (hipStream_t)s, drop_none(), x, ldx, w_qkv, ldw, b_qkv);
+  return attn_rows_fwd(d->heads, ab, d->P, d->ctx, d->ldc, d->alpha, (hipStream_t)s, drop, x, ldx, w_qkv, ldw, b_qkv);
 }
-int etp_attn_bwd_proj(const etp_attn_bwd_desc* d, const void* w_out, int64_t ldw, etp_stream_t s) {
-  ETP_REQUIRE(d && d->f.Q && d->f.K && d->f.V && d->f.P && d->dctx && d->dQ && d->dK && d->dV && w_out, "null pointer");
-  ETP_REQUIRE(d->f.ldS >= d->f.Lk && d->f.ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+int etp_attn_fwd_qkv_drop(const etp_attn_desc* d, const void* x, int64_t ldx, const void* w_qkv, int64_t ldw, const float* b_qkv,
+                          etp_stream_t s, const etp_drop_site* drop) {
+  return attn_fwd_qkv_body(__func__, d, x, ldx, w_qkv, ldw, b_qkv, s, drop);
+}
+int etp_attn_fwd_qkv(const etp_attn_desc* d, const void* x, int64_t ldx, const void* w_qkv, int64_t ldw, const float* b_qkv, etp_stream_t s) {
+  return attn_fwd_qkv_body(__func__, d, x, ldx, w_qkv, ldw, b_qkv, s, nullptr);
+}
+static int attn_bwd_proj_body(const char* who, const etp_attn_bwd_desc* d, const void* w_out, int64_t ldw, etp_stream_t s,
+                              const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, d && d->f.Q && d->f.K && d->f.V && d->f.P && d->dctx && d->dQ && d->dK && d->dV && w_out, "null pointer");
+  ETP_REQUIRE_AS(who, d->f.ldS >= d->f.Lk && d->f.ldS % 8 == 0, "ldS must be a multiple of 8 and >= Lk");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
   AttnBuf ab = to_buf(d->f);
   ab.O = d->f.ctx; ab.ldo = d->f.ldc;
   const int H = d->f.heads * 64;
   if (!(d->f.dtype == ETP_BF16 && attn_rows_ok(d->f.dtype, ab, d->f.ldc) && attn_rows_proj_ok(H, w_out, ldw))) {
-    set_error("etp_attn_bwd_proj: shape / dtype outside the fused kernel (bf16, Lq and Lk <= 128, heads*64 == 768)");
+    set_error(std::string(who) + ": shape / dtype outside the fused kernel (bf16, Lq and Lk <= 128, heads*64 == 768)");
     return ETP_ERR_INVALID;
   }
   return attn_rows_bwd(d->f.heads, ab, d->f.P, d->dctx, d->ldd, d->dQ, d->lddq, d->dK, d->lddk, d->dV, d->lddv, d->f.alpha, d->d_sp_w,
-                       d->d_sp_b, (hipStream_t)s, drop_none(), w_out, ldw, H);
+                       d->d_sp_b, (hipStream_t)s, drop, w_out, ldw, H);
+}
+int etp_attn_bwd_proj_drop(const etp_attn_bwd_desc* d, const void* w_out, int64_t ldw, etp_stream_t s, const etp_drop_site* drop) {
+  return attn_bwd_proj_body(__func__, d, w_out, ldw, s, drop);
+}
+int etp_attn_bwd_proj(const etp_attn_bwd_desc* d, const void* w_out, int64_t ldw, etp_stream_t s) {
+  return attn_bwd_proj_body(__func__, d, w_out, ldw, s, nullptr);
 }
 
+static int text_embed_fwd_body(const char* who, int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0,
+                               const float* gamma, const float* beta, float* y, void* y_lp, float* stats, int B, int L, int H, float eps,
+                               etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, ids && word && pos && type0 && gamma && beta && y && stats, "null pointer");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  return text_embed_fwd(dtype, ids, word, pos, type0, gamma, beta, y, y_lp, stats, B, L, H, eps, (hipStream_t)s, drop);
+}
+int etp_text_embed_fwd_drop(int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0, const float* gamma,
+                            const float* beta, float* y, void* y_lp, float* stats, int B, int L, int H, float eps, etp_stream_t s,
+                            const etp_drop_site* drop) {
+  return text_embed_fwd_body(__func__, dtype, ids, word, pos, type0, gamma, beta, y, y_lp, stats, B, L, H, eps, s, drop);
+}
 int etp_text_embed_fwd(int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0, const float* gamma,
                        const float* beta, float* y, void* y_lp, float* stats, int B, int L, int H, float eps, etp_stream_t s) {
-  ETP_REQUIRE(ids && word && pos && type0 && gamma && beta && y && stats, "null pointer");
-  return text_embed_fwd(dtype, ids, word, pos, type0, gamma, beta, y, y_lp, stats, B, L, H, eps, (hipStream_t)s);
+  return text_embed_fwd_body(__func__, dtype, ids, word, pos, type0, gamma, beta, y, y_lp, stats, B, L, H, eps, s, nullptr);
+}
+static int text_embed_bwd_body(const char* who, int dtype, const float* dy, const int64_t* ids, const float* word, const float* pos,
+                               const float* type0, const float* gamma, const float* stats, float* dword, float* dpos, float* dtype0,
+                               float* dgamma, float* dbeta, int B, int L, int H, etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, dy && ids && word && pos && type0 && gamma && stats && dword && dpos && dtype0 && dgamma && dbeta, "null pointer");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  return text_embed_bwd(dtype, dy, ids, word, pos, type0, gamma, stats, dword, dpos, dtype0, dgamma, dbeta, B, L, H, (hipStream_t)s, drop);
+}
+int etp_text_embed_bwd_drop(int dtype, const float* dy, const int64_t* ids, const float* word, const float* pos, const float* type0,
+                            const float* gamma, const float* stats, float* dword, float* dpos, float* dtype0, float* dgamma,
+                            float* dbeta, int B, int L, int H, etp_stream_t s, const etp_drop_site* drop) {
+  return text_embed_bwd_body(__func__, dtype, dy, ids, word, pos, type0, gamma, stats, dword, dpos, dtype0, dgamma, dbeta, B, L, H, s, drop);
 }
 int etp_text_embed_bwd(int dtype, const float* dy, const int64_t* ids, const float* word, const float* pos, const float* type0,
                        const float* gamma, const float* stats, float* dword, float* dpos, float* dtype0, float* dgamma,
                        float* dbeta, int B, int L, int H, etp_stream_t s) {
-  ETP_REQUIRE(dy && ids && word && pos && type0 && gamma && stats && dword && dpos && dtype0 && dgamma && dbeta, "null pointer");
-  return text_embed_bwd(dtype, dy, ids, word, pos, type0, gamma, stats, dword, dpos, dtype0, dgamma, dbeta, B, L, H, (hipStream_t)s);
+  return text_embed_bwd_body(__func__, dtype, dy, ids, word, pos, type0, gamma, stats, dword, dpos, dtype0, dgamma, dbeta, B, L, H, s, nullptr);
 }
 
 static PanoEmbedParams to_params(const float* const* p) {
   PanoEmbedParams q{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11]};
   return q;
 }
+static int pano_embed_fwd_body(const char* who, int dtype, const void* a, const void* d, const float* loc, const int64_t* nav,
+                               const float* const* params, float* y, float* stats, int M, int H, etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, a && loc && nav && params && y && stats, "null pointer");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  return pano_embed_fwd(dtype, a, d, loc, nav, to_params(params), y, stats, M, H, (hipStream_t)s, drop);
+}
+int etp_pano_embed_fwd_drop(int dtype, const void* a, const void* d, const float* loc, const int64_t* nav, const float* const* params,
+                            float* y, float* stats, int M, int H, etp_stream_t s, const etp_drop_site* drop) {
+  return pano_embed_fwd_body(__func__, dtype, a, d, loc, nav, params, y, stats, M, H, s, drop);
+}
 int etp_pano_embed_fwd(int dtype, const void* a, const void* d, const float* loc, const int64_t* nav, const float* const* params,
                        float* y, float* stats, int M, int H, etp_stream_t s) {
-  ETP_REQUIRE(a && loc && nav && params && y && stats, "null pointer");
-  return pano_embed_fwd(dtype, a, d, loc, nav, to_params(params), y, stats, M, H, (hipStream_t)s);
+  return pano_embed_fwd_body(__func__, dtype, a, d, loc, nav, params, y, stats, M, H, s, nullptr);
+}
+static int pano_embed_bwd_body(const char* who, int dtype, const float* dy, const void* a, const void* d, const float* loc,
+                               const int64_t* nav, const float* stats, const float* const* params, float* const* grads, void* da,
+                               void* dd, int M, int H, etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, dy && a && loc && nav && stats && params && grads && da && (d == nullptr || dd != nullptr), "null pointer");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  PanoEmbedGrads g{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10],
+                   grads[11]};
+  return pano_embed_bwd(dtype, dy, a, d, loc, nav, stats, to_params(params), g, da, dd, M, H, (hipStream_t)s, drop);
+}
+int etp_pano_embed_bwd_drop(int dtype, const float* dy, const void* a, const void* d, const float* loc, const int64_t* nav,
+                            const float* stats, const float* const* params, float* const* grads, void* da, void* dd, int M, int H,
+                            etp_stream_t s, const etp_drop_site* drop) {
+  return pano_embed_bwd_body(__func__, dtype, dy, a, d, loc, nav, stats, params, grads, da, dd, M, H, s, drop);
 }
 int etp_pano_embed_bwd(int dtype, const float* dy, const void* a, const void* d, const float* loc, const int64_t* nav,
                        const float* stats, const float* const* params, float* const* grads, void* da, void* dd, int M, int H,
                        etp_stream_t s) {
-  ETP_REQUIRE(dy && a && loc && nav && stats && params && grads && da && (d == nullptr || dd != nullptr), "null pointer");
-  PanoEmbedGrads g{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10],
-                   grads[11]};
-  return pano_embed_bwd(dtype, dy, a, d, loc, nav, stats, to_params(params), g, da, dd, M, H, (hipStream_t)s);
+  return pano_embed_bwd_body(__func__, dtype, dy, a, d, loc, nav, stats, params, grads, da, dd, M, H, s, nullptr);
 }
 int etp_gmap_embed_fwd(int dtype, const float* img, const int64_t* step_ids, const float* pos, const float* step_emb,
                        const float* w_pos, const float* b_pos, const float* gamma, const float* beta, float* x, void* x_lp,
@@ -420,16 +542,40 @@ int etp_gmap_embed_bwd(int dtype, const float* dx, const int64_t* step_ids, cons
   return gmap_embed_bwd(dtype, dx, step_ids, pos, w_pos, b_pos, gamma, stats, d_step_emb, d_w_pos, d_b_pos, dgamma, dbeta, M, H,
                         pos_dim, (hipStream_t)s);
 }
+static int sap_tail_fwd_body(const char* who, int dtype, const void* r, const float* gamma, const float* beta, const float* w2,
+                             const float* b2, const uint8_t* visited, const uint8_t* valid, float* logits, float* stats, int M, int H,
+                             etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, r && gamma && beta && w2 && b2 && logits && stats, "null pointer");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  return sap_tail_fwd(dtype, r, gamma, beta, w2, b2, visited, valid, logits, stats, M, H, (hipStream_t)s, drop);
+}
+int etp_sap_tail_fwd_drop(int dtype, const void* r, const float* gamma, const float* beta, const float* w2, const float* b2,
+                          const uint8_t* visited, const uint8_t* valid, float* logits, float* stats, int M, int H, etp_stream_t s,
+                          const etp_drop_site* drop) {
+  return sap_tail_fwd_body(__func__, dtype, r, gamma, beta, w2, b2, visited, valid, logits, stats, M, H, s, drop);
+}
 int etp_sap_tail_fwd(int dtype, const void* r, const float* gamma, const float* beta, const float* w2, const float* b2,
                      const uint8_t* visited, const uint8_t* valid, float* logits, float* stats, int M, int H, etp_stream_t s) {
-  ETP_REQUIRE(r && gamma && beta && w2 && b2 && logits && stats, "null pointer");
-  return sap_tail_fwd(dtype, r, gamma, beta, w2, b2, visited, valid, logits, stats, M, H, (hipStream_t)s);
+  return sap_tail_fwd_body(__func__, dtype, r, gamma, beta, w2, b2, visited, valid, logits, stats, M, H, s, nullptr);
+}
+static int sap_tail_bwd_body(const char* who, int dtype, const float* dlogits, const void* r, const float* gamma, const float* beta,
+                             const float* w2, const float* stats, const uint8_t* visited, const uint8_t* valid, void* dz, float* dgamma,
+                             float* dbeta, float* dw2, float* db2, int M, int H, etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, dlogits && r && gamma && beta && w2 && stats && dz && dgamma && dbeta && dw2 && db2, "null pointer");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  return sap_tail_bwd(dtype, dlogits, r, gamma, beta, w2, stats, visited, valid, dz, dgamma, dbeta, dw2, db2, M, H, (hipStream_t)s, drop);
+}
+int etp_sap_tail_bwd_drop(int dtype, const float* dlogits, const void* r, const float* gamma, const float* beta, const float* w2,
+                          const float* stats, const uint8_t* visited, const uint8_t* valid, void* dz, float* dgamma, float* dbeta,
+                          float* dw2, float* db2, int M, int H, etp_stream_t s, const etp_drop_site* drop) {
+  return sap_tail_bwd_body(__func__, dtype, dlogits, r, gamma, beta, w2, stats, visited, valid, dz, dgamma, dbeta, dw2, db2, M, H, s, drop);
 }
 int etp_sap_tail_bwd(int dtype, const float* dlogits, const void* r, const float* gamma, const float* beta, const float* w2,
                      const float* stats, const uint8_t* visited, const uint8_t* valid, void* dz, float* dgamma, float* dbeta,
                      float* dw2, float* db2, int M, int H, etp_stream_t s) {
-  ETP_REQUIRE(dlogits && r && gamma && beta && w2 && stats && dz && dgamma && dbeta && dw2 && db2, "null pointer");
-  return sap_tail_bwd(dtype, dlogits, r, gamma, beta, w2, stats, visited, valid, dz, dgamma, dbeta, dw2, db2, M, H, (hipStream_t)s);
+  return sap_tail_bwd_body(__func__, dtype, dlogits, r, gamma, beta, w2, stats, visited, valid, dz, dgamma, dbeta, dw2, db2, M, H, s, nullptr);
 }
 int etp_sap_ce(const float* logits, const int64_t* labels, float* loss, float* dlogits, int B, int G, float scale,
                int64_t ignore_index, etp_stream_t s) {
@@ -514,12 +660,20 @@ int etp_copy_f32(const float* src, float* dst, int64_t n, etp_stream_t s) {
   ETP_REQUIRE(((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "src / dst must be 16-byte aligned");
   return copy_f32(src, dst, (long)n, (hipStream_t)s);
 }
+static int cast_f32_to_body(const char* who, int dtype, const float* src, void* dst, int64_t n, etp_stream_t s, const etp_drop_site* site) {
+  ETP_REQUIRE_AS(who, dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
+  ETP_REQUIRE_AS(who, src && dst, "null pointer");
+  ETP_REQUIRE_AS(who, n >= 0 && n % 4 == 0, "n % 4 == 0 required");
+  ETP_REQUIRE_AS(who, ((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "src / dst must be 16-byte aligned");
+  Drop drop;
+  ETP_TRY(site_to_drop(who, site, drop));
+  return cast_drop(dtype, src, dst, (long)n, drop, (hipStream_t)s);
+}
+int etp_cast_f32_to_drop(int dtype, const float* src, void* dst, int64_t n, etp_stream_t s, const etp_drop_site* drop) {
+  return cast_f32_to_body(__func__, dtype, src, dst, n, s, drop);
+}
 int etp_cast_f32_to(int dtype, const float* src, void* dst, int64_t n, etp_stream_t s) {
-  ETP_REQUIRE(dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
-  ETP_REQUIRE(src && dst, "null pointer");
-  ETP_REQUIRE(n >= 0 && n % 4 == 0, "n % 4 == 0 required");
-  ETP_REQUIRE(((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "src / dst must be 16-byte aligned");
-  return cast_drop(dtype, src, dst, (long)n, drop_none(), (hipStream_t)s);
+  return cast_f32_to_body(__func__, dtype, src, dst, n, s, nullptr);
 }
 int etp_seq_mask(const int64_t* lens, uint8_t* m1, uint8_t* m2, int B, int V, etp_stream_t s) {
   ETP_REQUIRE(lens && m1, "null pointer");

@@ -496,6 +496,57 @@ int etp_planner_set_dropout(etp_planner* p, float p_hidden, float p_attn, float 
  * (panorama layers), 5 cross-attention probabilities, 6 cross-attention-output dense, 7 SAP head, 8 drop_env.
  * Needs no GPU. */
 int etp_dropout_multipliers(float p, uint64_t seed, int mode, int layer, int slot, int64_t n, float* out_host);
+/* One dropout site at operator level: the five numbers of etp_dropout_multipliers.  The `_drop` entry points below are the plain
+ * entry points of the same name with a trailing `const etp_drop_site*`; NULL or p == 0 is the plain call (the plain entry points
+ * ARE these calls with NULL).  p in [0, 1), mode >= 0, layer >= 0, 0 <= slot < 16, otherwise ETP_ERR_INVALID and nothing is launched.
+ * A backward call must name the site of its forward: the kernels regenerate the mask, none is stored.
+ * Element index each kernel hands to the generator (the `i` of etp_dropout_multipliers), all 32-bit -- a site's tensor must stay
+ * below 2^32 elements:
+ *   text / panorama embedding, SAP tail   row * H + col of the [M, H] row tensor: y (forward) and dy (backward) of the two
+ *                                         embeddings; the normalised row n of the SAP tail, forward and twice in its backward
+ *                                         (dw2 += dl * dropout(n), dn = dl * w2 * mask)
+ *   etp_ln_stream_bwd(_stage1)            row * H + col, on the operand copy dx_lp ONLY (dx, dgamma, dbeta stay undropped);
+ *                                         refused unless dx_lp is given and is not dx
+ *   etp_cast_f32_to                       the flat index
+ *   etp_gemm                              row * N + col of the M x N product (never ldc), on the epilogue value: bias -> activation ->
+ *                                         mask -> residual R -> store; Z of ETP_ACT_GELU_SAVEGRAD stays undropped, ETP_ACT_MUL_Z
+ *                                         masks (alpha A B^T) * Z.  ksplit > 1 or batch > 1 with dropout is refused.
+ *   etp_attn_*                            ((b * heads + h) * Lq + q) * Lk + key on the probabilities (never ldS): ctx = (P * mask) V,
+ *                                         dV = (P * mask)^T dctx, dP = (dctx V^T) * mask; the stored P stays undropped.  The batched-GEMM
+ *                                         family (etp_attn_family 0) writes the dropped copy to `Pd`, a second [B, heads, Lq, ldS]
+ *                                         buffer the backward reads again; it refuses dropout without it.  The other families
+ *                                         ignore `Pd`. */
+typedef struct etp_drop_site { float p; uint64_t seed; int32_t mode, layer, slot; } etp_drop_site;
+int etp_gemm_drop(const etp_gemm_desc* d, etp_stream_t stream, const etp_drop_site* drop);
+int etp_attn_fwd_drop(const etp_attn_desc* d, etp_stream_t stream, void* Pd, const etp_drop_site* drop);
+int etp_attn_bwd_drop(const etp_attn_bwd_desc* d, etp_stream_t stream, void* Pd, const etp_drop_site* drop);
+int etp_attn_fwd_qkv_drop(const etp_attn_desc* d, const void* x, int64_t ldx, const void* w_qkv, int64_t ldw, const float* b_qkv,
+                          etp_stream_t stream, const etp_drop_site* drop);
+int etp_attn_bwd_proj_drop(const etp_attn_bwd_desc* d, const void* w_out, int64_t ldw, etp_stream_t stream, const etp_drop_site* drop);
+int etp_ln_stream_bwd_drop(int dtype, const float* dy, const float* x, const float* stats, const float* gamma, const float* add,
+                           float* dx, void* dx_lp, float* dgamma, float* dbeta, int M, int H, etp_stream_t stream,
+                           const etp_drop_site* drop);
+int etp_ln_stream_bwd_stage1_drop(int dtype, const float* dy, const float* x, const float* stats, const float* gamma,
+                                  const float* add, float* dx, void* dx_lp, float* dgamma, float* dbeta, float* part, int M, int H,
+                                  etp_stream_t stream, const etp_drop_site* drop);
+int etp_text_embed_fwd_drop(int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0,
+                            const float* gamma, const float* beta, float* y, void* y_lp, float* stats, int B, int L, int H, float eps,
+                            etp_stream_t stream, const etp_drop_site* drop);
+int etp_text_embed_bwd_drop(int dtype, const float* dy, const int64_t* ids, const float* word, const float* pos, const float* type0,
+                            const float* gamma, const float* stats, float* dword, float* dpos, float* dtype0, float* dgamma,
+                            float* dbeta, int B, int L, int H, etp_stream_t stream, const etp_drop_site* drop);
+int etp_pano_embed_fwd_drop(int dtype, const void* a, const void* d, const float* loc, const int64_t* nav, const float* const* params,
+                            float* y, float* stats, int M, int H, etp_stream_t stream, const etp_drop_site* drop);
+int etp_pano_embed_bwd_drop(int dtype, const float* dy, const void* a, const void* d, const float* loc, const int64_t* nav,
+                            const float* stats, const float* const* params, float* const* grads, void* da, void* dd, int M, int H,
+                            etp_stream_t stream, const etp_drop_site* drop);
+int etp_sap_tail_fwd_drop(int dtype, const void* r, const float* gamma, const float* beta, const float* w2, const float* b2,
+                          const uint8_t* visited, const uint8_t* valid, float* logits, float* stats, int M, int H,
+                          etp_stream_t stream, const etp_drop_site* drop);
+int etp_sap_tail_bwd_drop(int dtype, const float* dlogits, const void* r, const float* gamma, const float* beta, const float* w2,
+                          const float* stats, const uint8_t* visited, const uint8_t* valid, void* dz, float* dgamma, float* dbeta,
+                          float* dw2, float* db2, int M, int H, etp_stream_t stream, const etp_drop_site* drop);
+int etp_cast_f32_to_drop(int dtype, const float* src, void* dst, int64_t n, etp_stream_t stream, const etp_drop_site* drop);
 /* bf16 mode: refresh the bf16 shadow of the GEMM weights from the fp32 masters (autocast's per-step weight cast). */
 int etp_planner_refresh_weights(etp_planner* p, etp_stream_t stream);
 /* The same refresh for one consumer only, so a multi-stream step can put each cast on the stream that first needs it:

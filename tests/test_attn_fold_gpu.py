@@ -16,9 +16,9 @@ own fp32 sums to bf16 at the same point, so it differs from the pair through the
 dctx); both are held to the bound the pair gets, elementwise, no multiplier.  The same inputs run twice give bit-identical dQ, dK, dV.
 Worst |got - fp64| / bound seen on the MI355X: dV 0.72, dQ 0.26, dK 0.24, the same for the pair and the fused launch on every shape.
 
-Not reachable through etp_attn_bwd_proj (it takes neither a dropout site nor kv_mod): attention dropout and the per-episode K/V
-indirection inside the fused kernel.  The planner-level suites run both through the fused backward (train-mode fixtures with
-B * heads <= CUs or Lq <= 64).
+Attention dropout inside the fused kernel: etp_attn_bwd_proj_drop, tests/test_drop_attn_gpu.py.  Not reachable through
+etp_attn_bwd_proj (it takes no kv_mod): the per-episode K/V indirection inside the fused kernel; the planner-level suites run it
+through the fused backward (train-mode fixtures with B * heads <= CUs or Lq <= 64).
 """
 import ctypes
 import math

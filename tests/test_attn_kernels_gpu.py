@@ -33,8 +33,8 @@ attn.hip attn_bwd_kernel `atomicAdd(a.d_sp_w, red[0] + ...)`, norm.hip softmax_b
 which workgroups retire.
 
 etp_attn_fwd_qkv (QKV projection folded into the register-resident forward): its ctx is held to attn_ref of the Q / K / V stash it wrote
-back, with the same bound.  Not reachable through the operator ABI, covered at planner level only: attention dropout and the kv_mod
-indirection.
+back, with the same bound.  Attention dropout: tests/test_drop_attn_gpu.py (etp_attn_*_drop); the kv_mod indirection:
+tests/test_attn_kv_steps_gpu.py.
 
 Worst |got - ref| / E observed on the MI355X (328 cases, 7 s; profiles/attn_op_bounds.txt has the whole table, the module prints it
 after its last case under pytest -s): ctx 0.85 and dV 0.79 (register-resident and LDS-tile bf16), dQ 0.40, dK 0.37 (LDS-tile bf16);

@@ -12,7 +12,7 @@ vlnce_baselines/models/etp/vilmodel_cmt.py and their autograd (include/etpnav_hi
 Contract cases that failed on the library before the vectorised epilogue required N % 8 == 0 and before split / batched products
 refused R, Z and activations: test_ragged_n_leaves_pad_columns_alone (pad columns N .. round_up(N, 8) - 1 of C and Z were written) and the
 "ksplit 2 / batch 2 with R / Z / act" entries of test_refusals (such calls were accepted and launched).
-Epilogue dropout stays planner-level: desc_to_args leaves GemmArgs::drop off at this ABI (COVERAGE.md)."""
+Epilogue dropout: tests/test_drop_gemm_gpu.py (etp_gemm_drop)."""
 import ctypes
 import functools
 import itertools
