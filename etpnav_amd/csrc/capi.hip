@@ -170,7 +170,7 @@ int check_hip(hipError_t e, const char* what) {
 
 using namespace etp;
 
-struct etp_graph { hipGraph_t graph; hipGraphExec_t exec; };
+struct etp_graph { hipGraph_t graph; hipGraphExec_t exec; GraphInfo* info; };   // info: recorded graphs only
 
 // etp_stamp: the stream's arrival time at this point, taken on the device (no host event, no profiler)
 __global__ void stamp_kernel(unsigned long long* slot) {
@@ -726,7 +726,7 @@ int etp_graph_end(etp_stream_t s, etp_graph** out) {
   ETP_CHECK_HIP(hipStreamEndCapture((hipStream_t)s, &g));
   hipGraphExec_t e;
   ETP_CHECK_HIP(hipGraphInstantiate(&e, g, nullptr, nullptr, 0));
-  *out = new etp_graph{g, e};
+  *out = new etp_graph{g, e, nullptr};
   return ETP_OK;
 }
 // Explicitly built graph (launch.h / graphrec.hip): between etp_rec_begin and etp_rec_end every call of this library that
@@ -738,11 +738,51 @@ int etp_rec_end(etp_graph** out, int64_t* n_kernels, int64_t* n_edges) {
   hipGraph_t g = nullptr;
   hipGraphExec_t e = nullptr;
   long nk = 0, ne = 0;
-  const int rc = rec_end(&g, &e, &nk, &ne);
-  if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+  GraphInfo* info = nullptr;
+  const int rc = rec_end(&g, &e, &nk, &ne, &info);
+  if (rc) { if (g) (void)hipGraphDestroy(g); delete info; return rc; }
   if (n_kernels) *n_kernels = nk;
   if (n_edges) *n_edges = ne;
-  *out = new etp_graph{g, e};
+  *out = new etp_graph{g, e, info};
+  return ETP_OK;
+}
+// Introspection of a recorded graph, all host-side (include/etpnav_hip.h)
+int etp_graph_info(etp_graph* g, int64_t* out) {
+  ETP_REQUIRE(g && g->info && out, "not a recorded graph");
+  std::vector<int32_t> f, t;
+  ETP_TRY(graph_edges(g->graph, *g->info, &f, &t));
+  out[0] = (int64_t)g->info->nodes.size();
+  out[1] = (int64_t)g->info->trace.size() / 4;
+  out[2] = (int64_t)f.size();
+  out[3] = g->info->n_streams;
+  return ETP_OK;
+}
+int etp_graph_trace(etp_graph* g, int32_t* rows, int64_t cap) {
+  ETP_REQUIRE(g && g->info && rows, "not a recorded graph");
+  ETP_REQUIRE(cap >= (int64_t)g->info->trace.size() / 4, "cap is below the number of trace rows");
+  memcpy(rows, g->info->trace.data(), g->info->trace.size() * sizeof(int32_t));
+  return ETP_OK;
+}
+int etp_graph_edges(etp_graph* g, int32_t* from, int32_t* to, int64_t cap) {
+  ETP_REQUIRE(g && g->info && from && to, "not a recorded graph");
+  std::vector<int32_t> f, t;
+  ETP_TRY(graph_edges(g->graph, *g->info, &f, &t));
+  ETP_REQUIRE(cap >= (int64_t)f.size(), "cap is below the number of edges");
+  memcpy(from, f.data(), f.size() * sizeof(int32_t));
+  memcpy(to, t.data(), t.size() * sizeof(int32_t));
+  return ETP_OK;
+}
+int etp_graph_node_name(etp_graph* g, int64_t i, char* buf, int cap) {
+  ETP_REQUIRE(g && g->info, "not a recorded graph");
+  return graph_node_name(*g->info, (long)i, buf, cap);
+}
+int etp_graph_linearize(etp_graph* g, const int32_t* order, int64_t n, etp_graph** out) {
+  ETP_REQUIRE(g && g->info && out, "not a recorded graph");
+  hipGraph_t ng = nullptr;
+  hipGraphExec_t ne = nullptr;
+  GraphInfo* ni = nullptr;
+  ETP_TRY(graph_linearize(g->graph, *g->info, order, (long)n, &ng, &ne, &ni));
+  *out = new etp_graph{ng, ne, ni};
   return ETP_OK;
 }
 int etp_rec_abort(void) { rec_abort(); return ETP_OK; }
@@ -755,6 +795,7 @@ int etp_graph_destroy(etp_graph* g) {
   if (!g) return ETP_OK;
   (void)hipGraphExecDestroy(g->exec);
   (void)hipGraphDestroy(g->graph);
+  delete g->info;
   delete g;
   return ETP_OK;
 }

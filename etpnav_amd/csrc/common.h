@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 
 #include "../../include/etpnav_hip.h"
 #include "launch.h"
@@ -219,9 +220,23 @@ bool gemm_uses_dma(int dtype, int K, int ksplit);   // true when launch_gemm wil
 // length (written to out, truncated to cap), or the refusal the launch itself would return
 int gemm_instance_query(int dtype, int c_dtype, int transA, int transB, const GemmArgs* gs, int n, int nbatch, char* out, int cap);
 // graphrec.hip: explicit hipGraph recording of everything issued through launch.h
+// What a recording leaves behind for etp_graph_info / _trace / _edges / _node_name / _linearize (host-side bookkeeping; the graph
+// itself is unchanged by it): the nodes in creation order, kind 0 kernel / 1 memset / 2 empty join node, and one row of four
+// int32 per call the recorder saw (kind, stream index, event index or -1, node index or -1; kinds 3 event record, 4 stream wait).
+struct GraphInfo {
+  std::vector<hipGraphNode_t> nodes;
+  std::vector<int> kinds;
+  std::vector<const void*> fns;      // kernel function of a kernel node (its name), null otherwise
+  std::vector<int32_t> trace;
+  int n_streams = 0;
+};
 int rec_begin();
-int rec_end(hipGraph_t* graph, hipGraphExec_t* exec, long* n_kernels, long* n_edges);
+int rec_end(hipGraph_t* graph, hipGraphExec_t* exec, long* n_kernels, long* n_edges, GraphInfo** info);
 void rec_abort();
+int graph_edges(hipGraph_t graph, const GraphInfo& info, std::vector<int32_t>* from, std::vector<int32_t>* to);
+int graph_node_name(const GraphInfo& info, long i, char* buf, int cap);
+int graph_linearize(hipGraph_t graph, const GraphInfo& info, const int32_t* order, long n, hipGraph_t* out_graph,
+                    hipGraphExec_t* out_exec, GraphInfo** out_info);
 void ktime_enable(bool on);
 void ktime_reset();
 long ktime_report(char* buf, long cap);

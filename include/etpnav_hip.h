@@ -1078,6 +1078,25 @@ int etp_rec_end(etp_graph** out, int64_t* n_kernels, int64_t* n_edges);
 int etp_rec_abort(void);
 int etp_graph_launch(etp_graph* g, etp_stream_t s);
 int etp_graph_destroy(etp_graph* g);
+/* Introspection of a graph built by etp_rec_end (host-side only; a captured graph returns ETP_ERR_INVALID).  A recording keeps its
+ * nodes in creation order (kernel nodes, memset nodes, the empty join nodes of event records made right after waits) and a trace of
+ * every call the recorder saw; both live until etp_graph_destroy.  None of it adds a node, an edge or an eager call.
+ *   etp_graph_info      out[0..3] = nodes, trace rows, edges (as the runtime reports them), logical streams.
+ *   etp_graph_trace     one row of 4 x int32 per recorded call, in call order: kind (0 kernel, 1 memset, 2 empty join node, 3 event
+ *                       record, 4 stream wait), stream index (by first appearance), event index (by first appearance) or -1, node
+ *                       index or -1.  A wait on an event that was never recorded inside the recording is traced too; the recorder
+ *                       ignores it (outside the recording that event is complete).  cap = rows the buffer holds.
+ *   etp_graph_edges     the edges hipGraphGetEdges reports, as creation indices (NOT the recorder's own dependency lists).
+ *   etp_graph_node_name the kernel's name, or "memset" / "join".
+ *   etp_graph_linearize a new graph of the same nodes with the same parameters whose only edges are order[i] -> order[i+1];
+ *                       `order` must be a permutation of all n nodes, anything else returns ETP_ERR_INVALID.  The result keeps the
+ *                       creation indices of `g` and is launched and destroyed like any etp_graph.  (tests/test_sched_gpu.py runs every
+ *                       order the recorded dependencies allow this way: a missing edge shows as a wrong result, without a race.) */
+int etp_graph_info(etp_graph* g, int64_t* out);
+int etp_graph_trace(etp_graph* g, int32_t* rows, int64_t cap);
+int etp_graph_edges(etp_graph* g, int32_t* from, int32_t* to, int64_t cap);
+int etp_graph_node_name(etp_graph* g, int64_t i, char* buf, int cap);
+int etp_graph_linearize(etp_graph* g, const int32_t* order, int64_t n, etp_graph** out);
 /* memset of `bytes` bytes.  value == 0 with bytes % 4 == 0 and p 16-byte aligned: the library's own zeroing kernel (float4 body, scalar
  * tail; recorded as a kernel node); everything else: the runtime's memset.  bytes = 0 does nothing. */
 int etp_memset_async(void* p, int value, int64_t bytes, etp_stream_t s);
