@@ -83,14 +83,12 @@ class ParamInfo(ctypes.Structure):
                 ("offset", ctypes.c_int64)]
 
 
-class ClipTensorInfo(ctypes.Structure):
+class TensorInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 128), ("ndim", ctypes.c_int32), ("shape", ctypes.c_int64 * 4),
                 ("offset", ctypes.c_int64)]
 
 
-class DepthTensorInfo(ctypes.Structure):
-    _fields_ = [("name", ctypes.c_char * 128), ("ndim", ctypes.c_int32), ("shape", ctypes.c_int64 * 4),
-                ("offset", ctypes.c_int64)]
+ClipTensorInfo = DepthTensorInfo = TensorInfo          # etp_clip_tensor_info / etp_depth_tensor_info: typedefs of etp_tensor_info
 
 
 class AdamwCfg(ctypes.Structure):

@@ -14,15 +14,13 @@ exercised only with a synthetic state dict of the same keys and shapes (tests/cl
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Dict, List
+from functools import partial
 
-import numpy as np
 import torch
-import torch.nn as nn
 
-from . import _lib
+from . import _lib, arena
 from ._lib import check, ptr
+from .arena import _edt, _stream
 
 NUM_IMGS, WIDTH, OUT_DIM, PATCH = 12, 768, 512, 32
 MEAN = (0.48145466, 0.4578275, 0.40821073)                # resnet_encoders.py:266
@@ -30,25 +28,8 @@ STD = (0.26862954, 0.26130258, 0.27577711)
 LN_EPS = 1e-5
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _require_gpu(t: torch.Tensor, what: str):
-    if t.device.type != "cuda":
-        raise _lib.EtpError(f"{what}: the CLIP encoder kernels need an MI355X (cuda/hip device); no CPU fallback exists")
-
-
-def _edt(dtype: torch.dtype) -> int:
-    return {torch.float32: _lib.ETP_F32, torch.bfloat16: _lib.ETP_BF16}[dtype]
-
-
-def _view_array(views: List[torch.Tensor]):
-    for v in views:
-        if v.dtype != torch.uint8:
-            raise TypeError(f"RGB observations must be uint8 [*, S, S, 3] (got {v.dtype})")
-        assert v.is_contiguous() and v.dim() == 4 and v.shape[3] == 3 and v.shape[1] == v.shape[2], tuple(v.shape)
-    return (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
+_require_gpu = partial(arena._require_gpu, kernels="CLIP encoder")
+_view_array = partial(arena._view_array, dtype=torch.uint8, channels=3, what="RGB")
 
 
 # ---- operator level -----------------------------------------------------------------------------------------------------------
@@ -83,13 +64,6 @@ def cls_ln(x, gamma, beta, out, N: int, S: int, eps: float = LN_EPS) -> torch.Te
 
 
 # ---- the encoder ----------------------------------------------------------------------------------------------------------------
-class _Node(nn.Module):
-    """Plain container reproducing OpenAI CLIP's module tree (state-dict names)."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("container module; call CLIPEncoder.forward")
-
-
 def _create(L, dtype, image_size, layers):
     h = L.etp_clip_create(_edt(dtype), int(image_size), int(layers))
     if not h:
@@ -97,98 +71,36 @@ def _create(L, dtype, image_size, layers):
     return h
 
 
-def _table(L, h):
-    info = _lib.ClipTensorInfo()
-    out = []
-    for i in range(L.etp_clip_param_count(h)):
-        check(L.etp_clip_param_info(h, i, ctypes.byref(info)), "etp_clip_param_info")
-        out.append((info.name.decode(), tuple(int(info.shape[k]) for k in range(info.ndim)), int(info.offset)))
-    return out
-
-
 def param_table(dtype: torch.dtype = torch.float32, image_size: int = 224, layers: int = 12):
     """[(OpenAI state-dict name without "visual.", shape, arena offset)] of the engine; needs the built library, not a GPU."""
     L = _lib.lib()
     h = _create(L, dtype, image_size, layers)
     try:
-        return _table(L, h)
+        return arena.read_table(L, "clip", h, _lib.ClipTensorInfo)
     finally:
         L.etp_clip_destroy(h)
 
 
-class CLIPEncoder(nn.Module):
+class CLIPEncoder(arena.FrozenArenaModule):
     """resnet_encoders.py:244-278 on the HIP engine.  Parameters are views of one flat fp32 arena under OpenAI CLIP's visual.* names
     (without the prefix), so ``load_state_dict`` is strict under those names and ``load_openai_state_dict`` takes a whole CLIP state
     dict.  image_size and layers exist so that tests can be small; the shipped encoder is (224, 12)."""
 
+    PREFIX, INFO = "clip", _lib.ClipTensorInfo
+
     def __init__(self, device=None, dtype: torch.dtype = torch.bfloat16, image_size: int = 224, layers: int = 12):
         super().__init__()
         assert dtype in (torch.float32, torch.bfloat16)
-        self.L = _lib.lib()
-        self.compute_dtype, self.image_size, self.layers = dtype, int(image_size), int(layers)
-        self.handle = _create(self.L, dtype, image_size, layers)
+        self.image_size, self.layers = int(image_size), int(layers)
         self.tokens = (self.image_size // PATCH) ** 2 + 1
         self.output_shape = (OUT_DIM,)
-        self.table = _table(self.L, self.handle)
-        self.total = int(self.L.etp_clip_arena_elems(self.handle))
-        self.n_matrix = int(self.L.etp_clip_matrix_elems(self.handle))
-        dev = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
-        self.arena = torch.zeros(self.total, dtype=torch.float32, device=dev)
-        self.shadow = None
-        self._shadow_version = -1
-        self._ws: Dict[int, torch.Tensor] = {}
-        self._views: List[tuple] = []
-        self._probe = None
-        for name, shape, off in self.table:
-            n = int(np.prod(shape))
-            p = nn.Parameter(self.arena[off:off + n].view(shape), requires_grad=False)
-            mod = self
-            parts = name.split(".")
-            for part in parts[:-1]:
-                if part not in mod._modules:
-                    mod.add_module(part, _Node())
-                mod = mod._modules[part]
-            mod.register_parameter(parts[-1], p)
-            self._views.append((p, off, n, shape))
-        self._bind()
+        self._init_arena(_create(_lib.lib(), dtype, image_size, layers), device, dtype)
         self.eval()
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.L.etp_clip_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-    def _bind(self):
-        if self.arena.device.type != "cuda":
-            return
-        if self.compute_dtype == torch.bfloat16:
-            self.shadow = torch.zeros(self.n_matrix, dtype=torch.bfloat16, device=self.arena.device)
-        check(self.L.etp_clip_bind(self.handle, ptr(self.arena), ptr(self.shadow)), "etp_clip_bind")
-        self._shadow_version = -1
-
-    def _apply(self, fn, recurse=True):
-        new = fn(self.arena)
-        if new.dtype != torch.float32:
-            raise TypeError("the encoder's master parameters stay fp32; choose the compute dtype at construction")
-        if new.device != self.arena.device:
-            with torch.no_grad():
-                self.arena = new.contiguous()
-                for p, off, n, shape in self._views:
-                    p.data = self.arena[off:off + n].view(shape)
-                self._ws.clear()
-                self.set_probe(False)
-                self._bind()
-        return self
+    def _on_move(self):
+        self.set_probe(False)
 
     # ---- loading ----
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        r = super().load_state_dict(state_dict, strict=strict, assign=False)
-        self._shadow_version = -1
-        return r
-
     def load_openai_state_dict(self, state_dict):
         """A whole CLIP state dict (clip.load(...)[0].state_dict()): keeps visual.*, ignores the text tower; strict on what it keeps.
         fp16 checkpoints (OpenAI's GPU default) are widened to the fp32 arena."""
@@ -206,23 +118,9 @@ class CLIPEncoder(nn.Module):
         return enc
 
     # ---- compute ----
-    def _version(self) -> int:
-        return self.arena._version + sum(p._version for p, _, _, _ in self._views)
-
-    def refresh_weights(self):
-        """Rebuild the bf16 shadow from the fp32 arena (done automatically when a parameter's version counter moved)."""
-        check(self.L.etp_clip_refresh_weights(self.handle, _stream()), "etp_clip_refresh_weights")
-        self._shadow_version = self._version()
-
     def _prepare(self, N: int):
         _require_gpu(self.arena, "CLIPEncoder")
-        if self.shadow is not None and self._version() != self._shadow_version:
-            self.refresh_weights()
-        ws = self._ws.get(N)
-        if ws is None:
-            ws = torch.empty(int(self.L.etp_clip_ws_bytes(self.handle, N)), dtype=torch.uint8, device=self.arena.device)
-            self._ws[N] = ws
-        return ws, torch.empty(N, OUT_DIM, dtype=torch.float32, device=self.arena.device)
+        return self._scratch(N), torch.empty(N, OUT_DIM, dtype=torch.float32, device=self.arena.device)
 
     def _check_views(self, views):
         for v in views:

@@ -21,77 +21,53 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "arena.h"
 #include "kernels.h"
 
 namespace etp {
-struct ClipInfo { std::string name; int ndim; long shape[4]; int region; long offset; long numel; };
 struct ClipLayer { int qkv_w, qkv_b, o_w, o_b, ln1_g, ln1_b, fc_w, fc_b, pj_w, pj_b, ln2_g, ln2_b; };
 constexpr int CL_W = 768, CL_I = 3072, CL_HEADS = 12, CL_PATCH = 32, CL_PK = 3072, CL_OUT = 512, CL_MAX_LAYERS = 12;
 constexpr float CL_LN_EPS = 1e-5f;
 }  // namespace etp
 
-struct etp_clip {
-  int dtype, S, layers, T;
-  std::vector<etp::ClipInfo> params;
-  long total = 0, n_matrix = 0;
+struct etp_clip : etp::ArenaEngine {
+  int S, layers, T;
   int conv_w, cls, pos, proj, pre_g, pre_b, post_g, post_b;
   etp::ClipLayer layer[etp::CL_MAX_LAYERS];
-  float* P = nullptr; void* Sh = nullptr;
   float* probe = nullptr;
-  const float* pf(int i) const { return P + params[i].offset; }
-  const void* pw(int i) const {
-    if (dtype == ETP_BF16) return reinterpret_cast<const uint16_t*>(Sh) + params[i].offset;
-    return P + params[i].offset;
-  }
 };
 
 namespace etp {
 
-static int cl_add(etp_clip* w, const std::string& name, int region, std::initializer_list<long> shape) {
-  ClipInfo p;
-  p.name = name; p.ndim = (int)shape.size(); p.region = region; p.numel = 1; p.offset = -1;
-  int k = 0;
-  for (long s : shape) { p.shape[k++] = s; p.numel *= s; }
-  for (; k < 4; ++k) p.shape[k] = 0;
-  w->params.push_back(p);
-  return (int)w->params.size() - 1;
-}
 
 // state-dict order of OpenAI's VisionTransformer (own parameters first, then conv1, ln_pre, transformer, ln_post); region 0 = GEMM
 // matrices (bf16 shadow), 1 = everything the kernels read as fp32
 static void cl_layout(etp_clip* w) {
-  w->cls = cl_add(w, "class_embedding", 1, {CL_W});
-  w->pos = cl_add(w, "positional_embedding", 1, {w->T, CL_W});
-  w->proj = cl_add(w, "proj", 0, {CL_W, CL_OUT});
-  w->conv_w = cl_add(w, "conv1.weight", 0, {CL_W, 3, CL_PATCH, CL_PATCH});
-  w->pre_g = cl_add(w, "ln_pre.weight", 1, {CL_W});
-  w->pre_b = cl_add(w, "ln_pre.bias", 1, {CL_W});
+  w->cls = w->table.add("class_embedding", 1, {CL_W});
+  w->pos = w->table.add("positional_embedding", 1, {w->T, CL_W});
+  w->proj = w->table.add("proj", 0, {CL_W, CL_OUT});
+  w->conv_w = w->table.add("conv1.weight", 0, {CL_W, 3, CL_PATCH, CL_PATCH});
+  w->pre_g = w->table.add("ln_pre.weight", 1, {CL_W});
+  w->pre_b = w->table.add("ln_pre.bias", 1, {CL_W});
   for (int l = 0; l < w->layers; ++l) {
     const std::string p = "transformer.resblocks." + std::to_string(l);
     ClipLayer& L = w->layer[l];
-    L.qkv_w = cl_add(w, p + ".attn.in_proj_weight", 0, {3 * CL_W, CL_W});
-    L.qkv_b = cl_add(w, p + ".attn.in_proj_bias", 1, {3 * CL_W});
-    L.o_w = cl_add(w, p + ".attn.out_proj.weight", 0, {CL_W, CL_W});
-    L.o_b = cl_add(w, p + ".attn.out_proj.bias", 1, {CL_W});
-    L.ln1_g = cl_add(w, p + ".ln_1.weight", 1, {CL_W});
-    L.ln1_b = cl_add(w, p + ".ln_1.bias", 1, {CL_W});
-    L.fc_w = cl_add(w, p + ".mlp.c_fc.weight", 0, {CL_I, CL_W});
-    L.fc_b = cl_add(w, p + ".mlp.c_fc.bias", 1, {CL_I});
-    L.pj_w = cl_add(w, p + ".mlp.c_proj.weight", 0, {CL_W, CL_I});
-    L.pj_b = cl_add(w, p + ".mlp.c_proj.bias", 1, {CL_W});
-    L.ln2_g = cl_add(w, p + ".ln_2.weight", 1, {CL_W});
-    L.ln2_b = cl_add(w, p + ".ln_2.bias", 1, {CL_W});
+    L.qkv_w = w->table.add(p + ".attn.in_proj_weight", 0, {3 * CL_W, CL_W});
+    L.qkv_b = w->table.add(p + ".attn.in_proj_bias", 1, {3 * CL_W});
+    L.o_w = w->table.add(p + ".attn.out_proj.weight", 0, {CL_W, CL_W});
+    L.o_b = w->table.add(p + ".attn.out_proj.bias", 1, {CL_W});
+    L.ln1_g = w->table.add(p + ".ln_1.weight", 1, {CL_W});
+    L.ln1_b = w->table.add(p + ".ln_1.bias", 1, {CL_W});
+    L.fc_w = w->table.add(p + ".mlp.c_fc.weight", 0, {CL_I, CL_W});
+    L.fc_b = w->table.add(p + ".mlp.c_fc.bias", 1, {CL_I});
+    L.pj_w = w->table.add(p + ".mlp.c_proj.weight", 0, {CL_W, CL_I});
+    L.pj_b = w->table.add(p + ".mlp.c_proj.bias", 1, {CL_W});
+    L.ln2_g = w->table.add(p + ".ln_2.weight", 1, {CL_W});
+    L.ln2_b = w->table.add(p + ".ln_2.bias", 1, {CL_W});
   }
-  w->post_g = cl_add(w, "ln_post.weight", 1, {CL_W});
-  w->post_b = cl_add(w, "ln_post.bias", 1, {CL_W});
-  long off = 0;
-  for (int region = 0; region < 2; ++region) {
-    for (auto& p : w->params)
-      if (p.region == region) { p.offset = off; off += round_up(p.numel, 64); }
-    if (region == 0) w->n_matrix = off;
-  }
-  w->total = off;
+  w->post_g = w->table.add("ln_post.weight", 1, {CL_W});
+  w->post_b = w->table.add("ln_post.bias", 1, {CL_W});
+  w->table.layout(2);
 }
 
 // the ONE scratch plan of etp_clip_fwd / etp_clip_fwd_views (NULL base: sizes only)
@@ -100,33 +76,25 @@ struct ClipScratch { void* rows; float* prod; float* xa; float* xb; void* xt; vo
 static ClipScratch cl_plan(const etp_clip* w, void* base, long N) {
   const size_t es = dtype_size(w->dtype);
   const size_t T = w->T, M = (size_t)N * T, NP = (size_t)N * (T - 1), ldS = round_up(T, 8);
-  char* b = reinterpret_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* p = b ? b + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  };
+  Bump b(base);
   ClipScratch s;
-  s.rows = take(NP * CL_PK * es);                   // normalised patch rows (operand dtype)
-  s.prod = (float*)take(NP * CL_W * 4);             // conv1 product
-  s.xa = (float*)take(M * CL_W * 4);                // residual stream (fp32), two buffers
-  s.xb = (float*)take(M * CL_W * 4);
-  s.xt = take(M * CL_W * es);                       // LayerNorm output = GEMM operand
-  s.qkv = take(M * 3 * CL_W * es);
-  s.P = take((size_t)N * CL_HEADS * T * ldS * es);  // attention probabilities / lse, whichever family runs
-  s.ctx = take(M * CL_W * es);
-  s.h = take(M * CL_I * es);
-  s.cls = take((size_t)N * CL_W * es);
-  s.bytes = off;
+  s.rows = b.take(NP * CL_PK * es);                   // normalised patch rows (operand dtype)
+  s.prod = (float*)b.take(NP * CL_W * 4);             // conv1 product
+  s.xa = (float*)b.take(M * CL_W * 4);                // residual stream (fp32), two buffers
+  s.xb = (float*)b.take(M * CL_W * 4);
+  s.xt = b.take(M * CL_W * es);                       // LayerNorm output = GEMM operand
+  s.qkv = b.take(M * 3 * CL_W * es);
+  s.P = b.take((size_t)N * CL_HEADS * T * ldS * es);  // attention probabilities / lse, whichever family runs
+  s.ctx = b.take(M * CL_W * es);
+  s.h = b.take(M * CL_I * es);
+  s.cls = b.take((size_t)N * CL_W * es);
+  s.bytes = b.off;
   return s;
 }
 
 static int cl_linear(const etp_clip* w, int c_dtype, const void* X, long ldx, int wi, int bi, void* Y, long ldy, long M, int N, int K,
                      const void* R, int tb, hipStream_t st) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.nb_inner = 1; g.ksplit = 1; g.alpha = 1.f; g.drop = drop_none();
+  GemmArgs g = base_args();
   g.A = X; g.lda = ldx; g.B = w->pw(wi); g.ldb = tb ? N : K; g.C = Y; g.ldc = ldy;
   g.M = (int)M; g.N = N; g.K = K;
   g.bias = bi >= 0 ? w->pf(bi) : nullptr;
@@ -186,30 +154,21 @@ etp_clip* etp_clip_create(int dtype, int image_size, int layers) {
   return w;
 }
 void etp_clip_destroy(etp_clip* w) { delete w; }
-int etp_clip_param_count(const etp_clip* w) { return w ? (int)w->params.size() : 0; }
+int etp_clip_param_count(const etp_clip* w) { return w ? w->table.size() : 0; }
 int etp_clip_param_info(const etp_clip* w, int i, etp_clip_tensor_info* out) {
-  ETP_REQUIRE(w && out && i >= 0 && i < (int)w->params.size(), "bad index");
-  const ClipInfo& q = w->params[i];
-  memset(out, 0, sizeof(*out));
-  strncpy(out->name, q.name.c_str(), sizeof(out->name) - 1);
-  out->ndim = q.ndim;
-  for (int k = 0; k < 4; ++k) out->shape[k] = q.shape[k];
-  out->offset = q.offset;
+  ETP_REQUIRE(w && out && i >= 0 && i < w->table.size(), "bad index");
+  w->table.fill(i, out);
   return ETP_OK;
 }
-int64_t etp_clip_arena_elems(const etp_clip* w) { return w ? w->total : 0; }
-int64_t etp_clip_matrix_elems(const etp_clip* w) { return w ? w->n_matrix : 0; }
+int64_t etp_clip_arena_elems(const etp_clip* w) { return w ? w->table.total : 0; }
+int64_t etp_clip_matrix_elems(const etp_clip* w) { return w ? w->table.n_matrix : 0; }
 int etp_clip_bind(etp_clip* w, float* params, void* shadow) {
-  ETP_REQUIRE(w && params, "null engine / params");
-  ETP_REQUIRE(w->dtype == ETP_F32 || shadow != nullptr, "bf16 mode needs a shadow arena");
-  ETP_REQUIRE(((uintptr_t)params % 256 == 0) && ((uintptr_t)shadow % 256 == 0), "arenas must be 256-byte aligned");
-  w->P = params; w->Sh = shadow;
-  return ETP_OK;
+  return bind_arenas(__func__, w, params, shadow, "null engine / params");
 }
 int etp_clip_refresh_weights(etp_clip* w, etp_stream_t stream) {
   ETP_REQUIRE(w && w->P, "engine not bound");
   if (w->dtype != ETP_BF16) return ETP_OK;
-  return cast_f32_to_bf16(w->P, w->Sh, w->n_matrix, (hipStream_t)stream);
+  return cast_f32_to_bf16(w->P, w->Wc, w->table.n_matrix, (hipStream_t)stream);
 }
 int64_t etp_clip_ws_bytes(const etp_clip* w, int N) {
   if (!w || N <= 0) return 0;

@@ -18,49 +18,35 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "arena.h"
 #include "kernels.h"
 
 namespace etp {
-struct DepthInfo { std::string name; int ndim; long shape[4]; int region; long offset; long numel; };
 struct DepthConv { int w, g, b, cin, cout, k, stride; };
 struct DepthBlock { DepthConv c[3]; DepthConv down; bool has_down; };
 constexpr int DP_MAX_BLOCKS = 24;
 constexpr float DP_GN_EPS = 1e-5f;
 }  // namespace etp
 
-struct etp_depth {
-  int dtype, S, bp, ng, blocks[4], n_blocks, fs, Cc;
-  std::vector<etp::DepthInfo> params;
-  long total = 0, n_matrix = 0;
+struct etp_depth : etp::ArenaEngine {
+  int S, bp, ng, blocks[4], n_blocks, fs, Cc;
   etp::DepthConv stem, comp;
   etp::DepthBlock block[etp::DP_MAX_BLOCKS];
   int block_layer[etp::DP_MAX_BLOCKS];
-  float* P = nullptr; void* Pk = nullptr;
   float* probe = nullptr;
-  const float* pf(int i) const { return P + params[i].offset; }
-  const void* pw(int i) const { return reinterpret_cast<const char*>(Pk) + params[i].offset * (dtype == ETP_BF16 ? 2 : 4); }
+  etp_depth() { copy_in_f32 = true; }          // the packed copy is the GEMM operand in either dtype
 };
 
 namespace etp {
 
-static int dp_add(etp_depth* w, const std::string& name, int region, std::initializer_list<long> shape) {
-  DepthInfo p;
-  p.name = name; p.ndim = (int)shape.size(); p.region = region; p.numel = 1; p.offset = -1;
-  int k = 0;
-  for (long s : shape) { p.shape[k++] = s; p.numel *= s; }
-  for (; k < 4; ++k) p.shape[k] = 0;
-  w->params.push_back(p);
-  return (int)w->params.size() - 1;
-}
 // "<conv>.weight", "<norm>.weight", "<norm>.bias": one bias-free convolution and its GroupNorm.  region 0 = GEMM matrices (packed copy),
 // 1 = everything the kernels read as fp32 (the stem's 7x7 weight included)
 static DepthConv dp_conv(etp_depth* w, const std::string& conv, const std::string& norm, int cin, int cout, int k, int stride, int region) {
   DepthConv c;
   c.cin = cin; c.cout = cout; c.k = k; c.stride = stride;
-  c.w = dp_add(w, conv + ".weight", region, {cout, cin, k, k});
-  c.g = dp_add(w, norm + ".weight", 1, {cout});
-  c.b = dp_add(w, norm + ".bias", 1, {cout});
+  c.w = w->table.add(conv + ".weight", region, {cout, cin, k, k});
+  c.g = w->table.add(norm + ".weight", 1, {cout});
+  c.b = w->table.add(norm + ".bias", 1, {cout});
   return c;
 }
 
@@ -87,13 +73,7 @@ static void dp_layout(etp_depth* w) {
   }
   w->n_blocks = nb;
   w->comp = dp_conv(w, "compression.0", "compression.1", inplanes, w->Cc, 3, 1, 0);
-  long off = 0;
-  for (int region = 0; region < 2; ++region) {
-    for (auto& p : w->params)
-      if (p.region == region) { p.offset = off; off += round_up(p.numel, 64); }
-    if (region == 0) w->n_matrix = off;
-  }
-  w->total = off;
+  w->table.layout(2);
 }
 
 // the ONE scratch plan of etp_depth_fwd / etp_depth_fwd_views (NULL base: sizes only); element counts come from a walk over the network
@@ -118,32 +98,24 @@ static DepthScratch dp_plan(const etp_depth* w, void* base, long N) {
   }
   mx(rows, N * H * H * 9 * w->comp.cin);
   mx(pre, N * H * H * w->comp.cout);
-  char* b = reinterpret_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* p = b ? b + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  };
+  Bump b(base);
   const int G = w->ng > 1 ? w->ng : 1;
   DepthScratch s;
-  s.x0 = take(act * es);                  // block input / output, alternating (operand dtype, NHWC)
-  s.x1 = take(act * es);
-  s.a1 = take(mid * es);                  // after the first and the second convolution of a block
-  s.a2 = take(mid * es);
-  s.rows = take(rows * es);               // im2col rows of the 3x3 convolutions / gathered rows of the strided downsample
-  s.pre = (float*)take(pre * 4);          // pre-norm product (fp32)
-  s.pre2 = (float*)take(pre * 4);         // the downsample branch's pre-norm product
-  s.st = (float*)take((size_t)N * G * 2 * 4);
-  s.st2 = (float*)take((size_t)N * G * 2 * 4);
-  s.bytes = off;
+  s.x0 = b.take(act * es);                  // block input / output, alternating (operand dtype, NHWC)
+  s.x1 = b.take(act * es);
+  s.a1 = b.take(mid * es);                  // after the first and the second convolution of a block
+  s.a2 = b.take(mid * es);
+  s.rows = b.take(rows * es);               // im2col rows of the 3x3 convolutions / gathered rows of the strided downsample
+  s.pre = (float*)b.take(pre * 4);          // pre-norm product (fp32)
+  s.pre2 = (float*)b.take(pre * 4);         // the downsample branch's pre-norm product
+  s.st = (float*)b.take((size_t)N * G * 2 * 4);
+  s.st2 = (float*)b.take((size_t)N * G * 2 * 4);
+  s.bytes = b.off;
   return s;
 }
 
 static int dp_gemm(const etp_depth* w, const void* X, int wi, float* Y, long M, int N, int K, hipStream_t st) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.nb_inner = 1; g.ksplit = 1; g.alpha = 1.f; g.drop = drop_none();
+  GemmArgs g = base_args();
   g.A = X; g.lda = K; g.B = w->pw(wi); g.ldb = K; g.C = Y; g.ldc = N;
   g.M = (int)M; g.N = N; g.K = K;
   g.act = ETP_ACT_NONE;
@@ -243,31 +215,23 @@ etp_depth* etp_depth_create(int dtype, int image_size, int base_planes, const in
   return w;
 }
 void etp_depth_destroy(etp_depth* w) { delete w; }
-int etp_depth_param_count(const etp_depth* w) { return w ? (int)w->params.size() : 0; }
+int etp_depth_param_count(const etp_depth* w) { return w ? w->table.size() : 0; }
 int etp_depth_param_info(const etp_depth* w, int i, etp_depth_tensor_info* out) {
-  ETP_REQUIRE(w && out && i >= 0 && i < (int)w->params.size(), "bad index");
-  const DepthInfo& q = w->params[i];
-  memset(out, 0, sizeof(*out));
-  strncpy(out->name, q.name.c_str(), sizeof(out->name) - 1);
-  out->ndim = q.ndim;
-  for (int k = 0; k < 4; ++k) out->shape[k] = q.shape[k];
-  out->offset = q.offset;
+  ETP_REQUIRE(w && out && i >= 0 && i < w->table.size(), "bad index");
+  w->table.fill(i, out);
   return ETP_OK;
 }
-int64_t etp_depth_arena_elems(const etp_depth* w) { return w ? w->total : 0; }
-int64_t etp_depth_matrix_elems(const etp_depth* w) { return w ? w->n_matrix : 0; }
+int64_t etp_depth_arena_elems(const etp_depth* w) { return w ? w->table.total : 0; }
+int64_t etp_depth_matrix_elems(const etp_depth* w) { return w ? w->table.n_matrix : 0; }
 int etp_depth_out_channels(const etp_depth* w) { return w ? w->Cc : 0; }
 int etp_depth_bind(etp_depth* w, float* params, void* packed) {
-  ETP_REQUIRE(w && params && packed, "null engine / params / packed");
-  ETP_REQUIRE(((uintptr_t)params % 256 == 0) && ((uintptr_t)packed % 256 == 0), "arenas must be 256-byte aligned");
-  w->P = params; w->Pk = packed;
-  return ETP_OK;
+  return bind_arenas(__func__, w, params, packed, "null engine / params / packed");
 }
 int etp_depth_refresh_weights(etp_depth* w, etp_stream_t stream) {
   ETP_REQUIRE(w && w->P, "engine not bound");
-  char* pk = reinterpret_cast<char*>(w->Pk);
+  char* pk = reinterpret_cast<char*>(w->Wc);
   const size_t es = dtype_size(w->dtype);
-  for (const DepthInfo& p : w->params)
+  for (const ParamEntry& p : w->table.e)
     if (p.region == 0)
       ETP_TRY(depth_pack(w->dtype, w->P + p.offset, pk + p.offset * es, (int)p.shape[0], (int)p.shape[1], (int)(p.shape[2] * p.shape[3]),
                          (hipStream_t)stream));

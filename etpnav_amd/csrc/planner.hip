@@ -18,6 +18,7 @@
 #include <functional>
 #include <vector>
 
+#include "arena.h"
 #include "kernels.h"
 
 namespace etp {
@@ -29,14 +30,10 @@ struct PanoLayerP { int in_w, in_b, out_w, out_b, l1_w, l1_b, l2_w, l2_b, n1_g, 
 struct XLayerP { int q_w, q_b, kv_w, kv_b, xo_w, xo_b, xln_g, xln_b; AttnP self; FfnP ffn;
                  AttnP lself; FfnP lffn; };      // language side (forward_lang2visn), pre-training variant only
 
-struct PInfo { std::string name; int ndim; long shape[2]; int region; long offset; long numel; };
-
 }  // namespace etp
 
-struct etp_planner {
+struct etp_planner : etp::ArenaEngine {       // dtype == cfg.dtype; Wc = the bf16 shadow
   etp_config cfg;
-  std::vector<etp::PInfo> params;
-  long total = 0, n_matrix = 0;
   // named indices
   int word, pos, type, emb_g, emb_b;
   std::vector<etp::TxtLayerP> txt;
@@ -47,8 +44,7 @@ struct etp_planner {
   std::vector<etp::XLayerP> xl;
   int sap0_w, sap0_b, sap2_g, sap2_b, sap4_w, sap4_b;
   int mlm_w, mlm_b, mlm_g, mlm_bb, mlm_vb;       // MLM head (pre-training variant), -1 otherwise
-  // bound arenas
-  float* P = nullptr; void* S = nullptr; float* G = nullptr;
+  float* G = nullptr;         // the bound gradient arena: the offsets of P
   // training-mode dropout (0 = eval): hidden / attention-probability / RGB-feature ("drop_env") rates and the step seed
   float p_hidden = 0.f, p_attn = 0.f, p_env = 0.f, p_head = 0.f;
   // 1: etp_nav_bwd / etp_pano_bwd leave their weight-gradient GEMMs running on the aux stream instead of joining them
@@ -89,33 +85,19 @@ struct etp_planner {
     return e;
   }
 
-  long off(int i) const { return params[i].offset; }
-  const float* pf(int i) const { return P + params[i].offset; }          // fp32 parameter
-  float* gf(int i) const { return G + params[i].offset; }                // fp32 gradient
-  const void* pw(int i) const {                                          // GEMM operand in compute dtype
-    if (cfg.dtype == ETP_BF16) return reinterpret_cast<const uint16_t*>(S) + params[i].offset;
-    return P + params[i].offset;
-  }
+  float* gf(int i) const { return G + table.e[i].offset; }              // fp32 gradient
 };
 
 namespace etp {
-
-static int add_param(etp_planner* pl, const std::string& name, long r, long c, int region) {
-  PInfo p;
-  p.name = name; p.ndim = c > 0 ? 2 : 1; p.shape[0] = r; p.shape[1] = c > 0 ? c : 0; p.region = region;
-  p.numel = c > 0 ? r * c : r; p.offset = -1;
-  pl->params.push_back(p);
-  return (int)pl->params.size() - 1;
-}
 
 // region 0: GEMM matrices, 1: vectors / small, 2: embedding tables
 static void build_layout(etp_planner* pl) {
   const etp_config& c = pl->cfg;
   const long H = c.hidden, I = c.inter;
-  auto mat = [&](const std::string& n, long r, long k) { return add_param(pl, n, r, k, 0); };
-  auto vec = [&](const std::string& n, long r) { return add_param(pl, n, r, 0, 1); };
-  auto small = [&](const std::string& n, long r, long k) { return add_param(pl, n, r, k, 1); };
-  auto table = [&](const std::string& n, long r, long k) { return add_param(pl, n, r, k, 2); };
+  auto mat = [&](const std::string& n, long r, long k) { return pl->table.add(n, 0, {r, k}); };
+  auto vec = [&](const std::string& n, long r) { return pl->table.add(n, 1, {r}); };
+  auto small = [&](const std::string& n, long r, long k) { return pl->table.add(n, 1, {r, k}); };
+  auto table = [&](const std::string& n, long r, long k) { return pl->table.add(n, 2, {r, k}); };
 
   pl->word = table("embeddings.word_embeddings.weight", c.vocab, H);
   pl->pos = table("embeddings.position_embeddings.weight", c.max_pos, H);
@@ -246,25 +228,8 @@ static void build_layout(etp_planner* pl) {
     pl->mlm_w = pl->mlm_b = pl->mlm_g = pl->mlm_bb = pl->mlm_vb = -1;
   }
 
-  long off = 0;
-  for (int region = 0; region < 3; ++region) {
-    for (auto& p : pl->params)
-      if (p.region == region) { p.offset = off; off += round_up(p.numel, 64); }
-    if (region == 0) pl->n_matrix = off;
-  }
-  pl->total = off;
+  pl->table.layout(3);
 }
-
-// ---- bump allocator over caller-provided stash / workspace -----------------------------
-struct Bump {
-  char* base; size_t off = 0;
-  explicit Bump(void* b) : base(reinterpret_cast<char*>(b)) {}
-  void* take(size_t bytes) {
-    void* p = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  }
-};
 
 struct Ctx {
   etp_planner* pl; hipStream_t st; int dt; size_t es;  // element size of T
@@ -353,13 +318,6 @@ static int finish_wgrads(const Ctx& c) {
   return join_wgrads(c);
 }
 
-static GemmArgs base_args() {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.nb_inner = 1; g.ksplit = 1; g.alpha = 1.f;
-  return g;
-}
-
 // Y[M,N] = act(X[M,K] . W[N,K]^T + b) (+R)
 static int linear_fwd(const Ctx& c, const void* X, long ldx, int wi, int bi, void* Y, long ldy, int M, int N, int K, int act,
                       void* Z, const void* R, long ldr, Drop drop = drop_none()) {
@@ -415,7 +373,7 @@ static int linear_wgrad(const Ctx& c, const void* dY, long ldy, const void* X, l
   g.M = N; g.N = K; g.K = M;
   // matrix-region gradients may be first-touch stores (etp_planner_set_grad_overwrite); tables (the tied MLM decoder adds
   // into the word-embedding gradient) always accumulate
-  const bool store = c.pl->grad_overwrite && c.pl->params[wi].region == 0;
+  const bool store = c.pl->grad_overwrite && c.pl->table.e[wi].region == 0;
   const bool group_on = opt_on(OPT_WGRAD_GROUP, true);
   if (c.wq && group_on && gemm_uses_dma(c.dt, M, 1)) {
     // grouped path: whole token reduction in one tile pass (no split-K: the group as a whole fills the chip), bias
@@ -863,27 +821,25 @@ etp_planner* etp_planner_create(const etp_config* cfg) {
   }
   etp_planner* pl = new etp_planner();
   pl->cfg = *cfg;
+  pl->dtype = cfg->dtype;
   build_layout(pl);
   return pl;
 }
 void etp_planner_destroy(etp_planner* p) { delete p; }
-int etp_planner_param_count(const etp_planner* p) { return p ? (int)p->params.size() : 0; }
+int etp_planner_param_count(const etp_planner* p) { return p ? p->table.size() : 0; }
 int etp_planner_param_info(const etp_planner* p, int i, etp_param_info* out) {
-  ETP_REQUIRE(p && out && i >= 0 && i < (int)p->params.size(), "bad index");
-  const PInfo& q = p->params[i];
-  memset(out, 0, sizeof(*out));
-  strncpy(out->name, q.name.c_str(), sizeof(out->name) - 1);
-  out->ndim = q.ndim; out->shape[0] = q.shape[0]; out->shape[1] = q.shape[1]; out->offset = q.offset;
+  ETP_REQUIRE(p && out && i >= 0 && i < p->table.size(), "bad index");
+  p->table.fill(i, out);
   return ETP_OK;
 }
-int64_t etp_planner_arena_elems(const etp_planner* p) { return p ? p->total : 0; }
-int64_t etp_planner_matrix_elems(const etp_planner* p) { return p ? p->n_matrix : 0; }
+int64_t etp_planner_arena_elems(const etp_planner* p) { return p ? p->table.total : 0; }
+int64_t etp_planner_matrix_elems(const etp_planner* p) { return p ? p->table.n_matrix : 0; }
 int etp_planner_bind(etp_planner* p, float* params, void* shadow, float* grads) {
   ETP_REQUIRE(p && params, "null planner/params");
   ETP_REQUIRE(p->cfg.dtype == ETP_F32 || shadow != nullptr, "bf16 mode needs a shadow arena");
   ETP_REQUIRE(((uintptr_t)params % 256 == 0) && ((uintptr_t)shadow % 256 == 0) && ((uintptr_t)grads % 256 == 0),
               "arenas must be 256-byte aligned");
-  p->P = params; p->S = shadow; p->G = grads;
+  p->P = params; p->Wc = shadow; p->G = grads;
   return ETP_OK;
 }
 int etp_planner_set_aux_stream(etp_planner* p, etp_stream_t aux) {
@@ -929,7 +885,7 @@ int etp_dropout_multipliers(float p, uint64_t seed, int mode, int layer, int slo
 int etp_planner_refresh_weights(etp_planner* p, etp_stream_t stream) {
   ETP_REQUIRE(p && p->P, "planner not bound");
   if (p->cfg.dtype != ETP_BF16) return ETP_OK;
-  return cast_f32_to_bf16(p->P, p->S, p->n_matrix, (hipStream_t)stream);
+  return cast_f32_to_bf16(p->P, p->Wc, p->table.n_matrix, (hipStream_t)stream);
 }
 int etp_planner_refresh_part(etp_planner* p, int part, etp_stream_t stream) {
   ETP_REQUIRE(p && p->P && part >= 0 && part <= 2, "planner not bound / part must be 0 (text), 1 (panorama) or 2 (navigation)");
@@ -938,9 +894,9 @@ int etp_planner_refresh_part(etp_planner* p, int part, etp_stream_t stream) {
   const long txt_end = p->off(p->img_w);
   const long pano_end = p->cfg.n_x > 0 ? p->off(p->xl[0].self.qkv_w) : p->off(p->sap0_w);
   const long lo = part == 0 ? 0 : part == 1 ? txt_end : pano_end;
-  const long hi = part == 0 ? txt_end : part == 1 ? pano_end : p->n_matrix;
+  const long hi = part == 0 ? txt_end : part == 1 ? pano_end : p->table.n_matrix;
   if (hi <= lo) return ETP_OK;
-  return cast_f32_to_bf16(p->P + lo, reinterpret_cast<uint16_t*>(p->S) + lo, hi - lo, (hipStream_t)stream);
+  return cast_f32_to_bf16(p->P + lo, reinterpret_cast<uint16_t*>(p->Wc) + lo, hi - lo, (hipStream_t)stream);
 }
 
 // bf16 shadow of the text encoder with only layer 0 on the dependent chain: layer 0's matrices are cast on `main`, layers
@@ -951,12 +907,12 @@ int etp_planner_refresh_text_split(etp_planner* p, etp_stream_t main, etp_stream
   if (p->cfg.dtype != ETP_BF16) return ETP_OK;
   const long txt_end = p->off(p->img_w);
   hipStream_t sm = (hipStream_t)main, ss = (hipStream_t)side;
-  if (p->cfg.n_l < 2 || ss == nullptr || ss == sm) return cast_f32_to_bf16(p->P, p->S, txt_end, sm);
+  if (p->cfg.n_l < 2 || ss == nullptr || ss == sm) return cast_f32_to_bf16(p->P, p->Wc, txt_end, sm);
   const long l1 = p->off(p->txt[1].att.qkv_w);
-  ETP_TRY(cast_f32_to_bf16(p->P, p->S, l1, sm));
+  ETP_TRY(cast_f32_to_bf16(p->P, p->Wc, l1, sm));
   ETP_TRY(stream_after(p, sm, ss));                     // the side stream starts no earlier than this step (ordering with the optimizer)
   // (round 6: layer 0's cast on the side stream too, beside the embedding kernel: 3.949 against 3.931 ms, no gain -- r06_ab_runs.json r6c11)
-  ETP_TRY(cast_f32_to_bf16(p->P + l1, reinterpret_cast<uint16_t*>(p->S) + l1, txt_end - l1, ss));
+  ETP_TRY(cast_f32_to_bf16(p->P + l1, reinterpret_cast<uint16_t*>(p->Wc) + l1, txt_end - l1, ss));
   if (!p->txt_w_ready) ETP_CHECK_HIP(hipEventCreateWithFlags(&p->txt_w_ready, hipEventDisableTiming));
   ETP_CHECK_HIP(event_record(p->txt_w_ready, ss));
   p->txt_w_pending = true;

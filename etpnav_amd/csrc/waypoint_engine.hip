@@ -16,48 +16,30 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "arena.h"
 #include "kernels.h"
 
 namespace etp {
-struct WpInfo { std::string name; int ndim; long shape[2]; int region; long offset; long numel; };
 struct WpLayer { int qkv_w, qkv_b, o_w, o_b, ln1_g, ln1_b, i_w, i_b, d_w, d_b, ln2_g, ln2_b; };
 constexpr int WP_H = 768, WP_I = 3072, WP_DEPTH = 2048, WP_OUT = 120, WP_LAYERS = 2, WP_NEIGHBOR = 1;
 constexpr float WP_LN_EPS = 1e-12f;
 }  // namespace etp
 
-struct etp_waypoint {
-  int dtype;
-  std::vector<etp::WpInfo> params;
-  long total = 0, n_matrix = 0;
+struct etp_waypoint : etp::ArenaEngine {
   int fc_w, fc_b, c1_w, c1_b, c2_w, c2_b;
   etp::WpLayer layer[etp::WP_LAYERS];
-  float* P = nullptr; void* S = nullptr;
-  const float* pf(int i) const { return P + params[i].offset; }
-  const void* pw(int i) const {
-    if (dtype == ETP_BF16) return reinterpret_cast<const uint16_t*>(S) + params[i].offset;
-    return P + params[i].offset;
-  }
 };
 
 namespace etp {
 
-static int wp_add(etp_waypoint* w, const std::string& name, long r, long c, int region) {
-  WpInfo p;
-  p.name = name; p.ndim = c > 0 ? 2 : 1; p.shape[0] = r; p.shape[1] = c > 0 ? c : 0; p.region = region;
-  p.numel = c > 0 ? r * c : r; p.offset = -1;
-  w->params.push_back(p);
-  return (int)w->params.size() - 1;
-}
-
 // state-dict order of the reference module (TRM_net.py:27-60); region 0 = GEMM matrices (bf16 shadow), 1 = vectors.  The two
 // modules the forward never uses (visual_merge, mergefeats_LayerNorm) are in the table so that a strict load sees every key.
 static void wp_layout(etp_waypoint* w) {
-  auto mat = [&](const std::string& n, long r, long k) { return wp_add(w, n, r, k, 0); };
-  auto vec = [&](const std::string& n, long r) { return wp_add(w, n, r, 0, 1); };
+  auto mat = [&](const std::string& n, long r, long k) { return w->table.add(n, 0, {r, k}); };
+  auto vec = [&](const std::string& n, long r) { return w->table.add(n, 1, {r}); };
   w->fc_w = mat("visual_fc_depth.1.weight", WP_H, WP_DEPTH);
   w->fc_b = vec("visual_fc_depth.1.bias", WP_H);
-  wp_add(w, "visual_merge.0.weight", WP_H, 2 * WP_H, 1);                 // unused: kept out of the shadow region
+  w->table.add("visual_merge.0.weight", 1, {WP_H, 2 * WP_H});                // unused: kept out of the shadow region
   vec("visual_merge.0.bias", WP_H);
   for (int l = 0; l < WP_LAYERS; ++l) {
     const std::string p = "waypoint_TRM.bert.encoder.layer." + std::to_string(l);
@@ -87,13 +69,7 @@ static void wp_layout(etp_waypoint* w) {
   w->c2_b = vec("vis_classifier.2.bias", WP_OUT);
   // matrices first, in declaration order: query / key / value of a layer are adjacent (768 * 768 is a multiple of 64), so the three
   // are one [2304, 768] operand; the same holds for their biases in the vector region
-  long off = 0;
-  for (int region = 0; region < 2; ++region) {
-    for (auto& p : w->params)
-      if (p.region == region) { p.offset = off; off += round_up(p.numel, 64); }
-    if (region == 0) w->n_matrix = off;
-  }
-  w->total = off;
+  w->table.layout(2);
 }
 
 // the ONE scratch plan of etp_waypoint_fwd (NULL base: sizes only)
@@ -102,36 +78,28 @@ struct WpScratch { void* dep; float* xf; void* xt; void* qkv; void* ctx; float* 
 static WpScratch wp_plan(int dt, void* base, int B) {
   const size_t es = dtype_size(dt);
   const size_t M = (size_t)B * 12;
-  char* b = reinterpret_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* p = b ? b + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  };
+  Bump b(base);
   WpScratch s;
-  s.dep = dt == ETP_BF16 ? take(M * WP_DEPTH * es) : nullptr;      // operand copy of depth_feats
-  s.xf = (float*)take(M * WP_H * 4);                               // residual stream (fp32) ...
-  s.xt = dt == ETP_BF16 ? take(M * WP_H * es) : (void*)s.xf;       // ... and its GEMM-operand copy
-  s.qkv = take(M * 3 * WP_H * es);
-  s.ctx = take(M * WP_H * es);
-  s.s = (float*)take(M * WP_H * 4);                                // pre-LayerNorm sums
-  s.af = (float*)take(M * WP_H * 4);
-  s.at = dt == ETP_BF16 ? take(M * WP_H * es) : (void*)s.af;
-  s.h = take(M * WP_I * es);
-  s.z = take(M * WP_I * es);                                       // the GELU epilogue's second output (unused: no backward)
-  s.r = take(M * WP_H * es);                                       // classifier hidden
-  s.stats = (float*)take(M * 2 * 4);
-  s.raw = (float*)take(M * WP_OUT * 4);                            // logits before the roll
-  s.bytes = off;
+  s.dep = dt == ETP_BF16 ? b.take(M * WP_DEPTH * es) : nullptr;      // operand copy of depth_feats
+  s.xf = (float*)b.take(M * WP_H * 4);                               // residual stream (fp32) ...
+  s.xt = dt == ETP_BF16 ? b.take(M * WP_H * es) : (void*)s.xf;       // ... and its GEMM-operand copy
+  s.qkv = b.take(M * 3 * WP_H * es);
+  s.ctx = b.take(M * WP_H * es);
+  s.s = (float*)b.take(M * WP_H * 4);                                // pre-LayerNorm sums
+  s.af = (float*)b.take(M * WP_H * 4);
+  s.at = dt == ETP_BF16 ? b.take(M * WP_H * es) : (void*)s.af;
+  s.h = b.take(M * WP_I * es);
+  s.z = b.take(M * WP_I * es);                                       // the GELU epilogue's second output (unused: no backward)
+  s.r = b.take(M * WP_H * es);                                       // classifier hidden
+  s.stats = (float*)b.take(M * 2 * 4);
+  s.raw = (float*)b.take(M * WP_OUT * 4);                            // logits before the roll
+  s.bytes = b.off;
   return s;
 }
 
 static int wp_linear(const etp_waypoint* w, int c_dtype, const void* X, long ldx, int wi, int bi, void* Y, long ldy, int M, int N,
                      int K, int act, void* Z, const void* R, hipStream_t st) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.nb_inner = 1; g.ksplit = 1; g.alpha = 1.f; g.drop = drop_none();
+  GemmArgs g = base_args();
   g.A = X; g.lda = ldx; g.B = w->pw(wi); g.ldb = K; g.C = Y; g.ldc = ldy;
   g.M = M; g.N = N; g.K = K;
   g.bias = w->pf(bi);
@@ -153,28 +121,21 @@ etp_waypoint* etp_waypoint_create(int dtype) {
   return w;
 }
 void etp_waypoint_destroy(etp_waypoint* w) { delete w; }
-int etp_waypoint_param_count(const etp_waypoint* w) { return w ? (int)w->params.size() : 0; }
+int etp_waypoint_param_count(const etp_waypoint* w) { return w ? w->table.size() : 0; }
 int etp_waypoint_param_info(const etp_waypoint* w, int i, etp_param_info* out) {
-  ETP_REQUIRE(w && out && i >= 0 && i < (int)w->params.size(), "bad index");
-  const WpInfo& q = w->params[i];
-  memset(out, 0, sizeof(*out));
-  strncpy(out->name, q.name.c_str(), sizeof(out->name) - 1);
-  out->ndim = q.ndim; out->shape[0] = q.shape[0]; out->shape[1] = q.shape[1]; out->offset = q.offset;
+  ETP_REQUIRE(w && out && i >= 0 && i < w->table.size(), "bad index");
+  w->table.fill(i, out);
   return ETP_OK;
 }
-int64_t etp_waypoint_arena_elems(const etp_waypoint* w) { return w ? w->total : 0; }
-int64_t etp_waypoint_matrix_elems(const etp_waypoint* w) { return w ? w->n_matrix : 0; }
+int64_t etp_waypoint_arena_elems(const etp_waypoint* w) { return w ? w->table.total : 0; }
+int64_t etp_waypoint_matrix_elems(const etp_waypoint* w) { return w ? w->table.n_matrix : 0; }
 int etp_waypoint_bind(etp_waypoint* w, float* params, void* shadow) {
-  ETP_REQUIRE(w && params, "null engine / params");
-  ETP_REQUIRE(w->dtype == ETP_F32 || shadow != nullptr, "bf16 mode needs a shadow arena");
-  ETP_REQUIRE(((uintptr_t)params % 256 == 0) && ((uintptr_t)shadow % 256 == 0), "arenas must be 256-byte aligned");
-  w->P = params; w->S = shadow;
-  return ETP_OK;
+  return bind_arenas(__func__, w, params, shadow, "null engine / params");
 }
 int etp_waypoint_refresh_weights(etp_waypoint* w, etp_stream_t stream) {
   ETP_REQUIRE(w && w->P, "engine not bound");
   if (w->dtype != ETP_BF16) return ETP_OK;
-  return cast_f32_to_bf16(w->P, w->S, w->n_matrix, (hipStream_t)stream);
+  return cast_f32_to_bf16(w->P, w->Wc, w->table.n_matrix, (hipStream_t)stream);
 }
 int64_t etp_waypoint_ws_bytes(const etp_waypoint* w, int B) {
   if (!w || B <= 0) return 0;

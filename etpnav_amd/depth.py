@@ -19,39 +19,22 @@ to habitat's own classes.
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Sequence
+from functools import partial
+from typing import Sequence
 
-import numpy as np
 import torch
-import torch.nn as nn
 
-from . import _lib
+from . import _lib, arena
 from ._lib import check, ptr
+from .arena import _edt, _stream
 
 NUM_IMGS = 12
 GN_EPS = 1e-5
 DEFAULT_BLOCKS = (3, 4, 6, 3)
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _require_gpu(t: torch.Tensor, what: str):
-    if t.device.type != "cuda":
-        raise _lib.EtpError(f"{what}: the depth encoder kernels need an MI355X (cuda/hip device); no CPU fallback exists")
-
-
-def _edt(dtype: torch.dtype) -> int:
-    return {torch.float32: _lib.ETP_F32, torch.bfloat16: _lib.ETP_BF16}[dtype]
-
-
-def _view_array(views: List[torch.Tensor]):
-    for v in views:
-        if v.dtype != torch.float32:
-            raise TypeError(f"depth observations must be float32 [*, S, S, 1] (got {v.dtype})")
-        assert v.is_contiguous() and v.dim() == 4 and v.shape[3] == 1 and v.shape[1] == v.shape[2], tuple(v.shape)
-    return (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
+_require_gpu = partial(arena._require_gpu, kernels="depth encoder")
+_view_array = partial(arena._view_array, dtype=torch.float32, channels=1, what="depth")
 
 
 # ---- operator level -----------------------------------------------------------------------------------------------------------
@@ -103,13 +86,6 @@ def conv_rows(x: torch.Tensor, out: torch.Tensor, k: int, stride: int) -> torch.
 
 
 # ---- the encoder ----------------------------------------------------------------------------------------------------------------
-class _Node(nn.Module):
-    """Plain container reproducing habitat's module tree (state-dict names)."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("container module; call DepthEncoder.forward")
-
-
 def _create(L, dtype, image_size, base_planes, blocks: Sequence[int]):
     if len(blocks) != 4:
         raise _lib.EtpError("etp_depth_create: four block counts are needed")
@@ -120,99 +96,38 @@ def _create(L, dtype, image_size, base_planes, blocks: Sequence[int]):
     return h
 
 
-def _table(L, h):
-    info = _lib.DepthTensorInfo()
-    out = []
-    for i in range(L.etp_depth_param_count(h)):
-        check(L.etp_depth_param_info(h, i, ctypes.byref(info)), "etp_depth_param_info")
-        out.append((info.name.decode(), tuple(int(info.shape[k]) for k in range(info.ndim)), int(info.offset)))
-    return out
-
-
 def param_table(dtype: torch.dtype = torch.float32, image_size: int = 256, base_planes: int = 32, blocks: Sequence[int] = DEFAULT_BLOCKS):
     """[(state-dict name, shape, arena offset)] of the engine; needs the built library, not a GPU."""
     L = _lib.lib()
     h = _create(L, dtype, image_size, base_planes, blocks)
     try:
-        return _table(L, h)
+        return arena.read_table(L, "depth", h, _lib.DepthTensorInfo)
     finally:
         L.etp_depth_destroy(h)
 
 
-class DepthEncoder(nn.Module):
+class DepthEncoder(arena.FrozenArenaModule):
     """resnet_encoders.py:13-107 on the HIP engine.  Parameters are frozen views of one flat fp32 arena under the names of
     VlnResnetDepthEncoder.visual_encoder's state dict (backbone.conv1.0.weight ... compression.1.bias), so ``load_state_dict`` is strict
     under those names and ``load_ddppo_state_dict`` takes a DD-PPO checkpoint's state dict.  image_size, base_planes and blocks exist so
     that tests can be small; the shipped encoder is (256, 32, (3, 4, 6, 3))."""
 
+    PREFIX, INFO, COPY, COPY_IN_F32 = "depth", _lib.DepthTensorInfo, "packed", True
+
     def __init__(self, device=None, dtype: torch.dtype = torch.bfloat16, image_size: int = 256, base_planes: int = 32,
                  blocks: Sequence[int] = DEFAULT_BLOCKS):
         super().__init__()
         assert dtype in (torch.float32, torch.bfloat16)
-        self.L = _lib.lib()
-        self.compute_dtype, self.image_size, self.base_planes, self.blocks = dtype, int(image_size), int(base_planes), tuple(blocks)
-        self.handle = _create(self.L, dtype, image_size, base_planes, blocks)
+        self.image_size, self.base_planes, self.blocks = int(image_size), int(base_planes), tuple(blocks)
+        self._init_arena(_create(_lib.lib(), dtype, image_size, base_planes, blocks), device, dtype)
         fs = self.image_size // 64
         self.output_shape = (int(self.L.etp_depth_out_channels(self.handle)), fs, fs)
-        self.table = _table(self.L, self.handle)
-        self.total = int(self.L.etp_depth_arena_elems(self.handle))
-        self.n_matrix = int(self.L.etp_depth_matrix_elems(self.handle))
-        dev = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
-        self.arena = torch.zeros(self.total, dtype=torch.float32, device=dev)
-        self.packed = None
-        self._packed_version = -1
-        self._ws: Dict[int, torch.Tensor] = {}
-        self._views: List[tuple] = []
-        self._probe = None
-        for name, shape, off in self.table:
-            n = int(np.prod(shape))
-            p = nn.Parameter(self.arena[off:off + n].view(shape), requires_grad=False)
-            mod = self
-            parts = name.split(".")
-            for part in parts[:-1]:
-                if part not in mod._modules:
-                    mod.add_module(part, _Node())
-                mod = mod._modules[part]
-            mod.register_parameter(parts[-1], p)
-            self._views.append((p, off, n, shape))
-        self._bind()
         self.eval()
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.L.etp_depth_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-    def _bind(self):
-        if self.arena.device.type != "cuda":
-            return
-        self.packed = torch.zeros(self.n_matrix, dtype=self.compute_dtype, device=self.arena.device)
-        check(self.L.etp_depth_bind(self.handle, ptr(self.arena), ptr(self.packed)), "etp_depth_bind")
-        self._packed_version = -1
-
-    def _apply(self, fn, recurse=True):
-        new = fn(self.arena)
-        if new.dtype != torch.float32:
-            raise TypeError("the encoder's master parameters stay fp32; choose the compute dtype at construction")
-        if new.device != self.arena.device:
-            with torch.no_grad():
-                self.arena = new.contiguous()
-                for p, off, n, shape in self._views:
-                    p.data = self.arena[off:off + n].view(shape)
-                self._ws.clear()
-                self.set_probe(False)
-                self._bind()
-        return self
+    def _on_move(self):
+        self.set_probe(False)
 
     # ---- loading ----
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        r = super().load_state_dict(state_dict, strict=strict, assign=False)
-        self._packed_version = -1
-        return r
-
     def load_ddppo_state_dict(self, state_dict):
         """A DD-PPO checkpoint's state dict (torch.load(path)["state_dict"]), filtered as resnet_encoders.py:40-50 does: of every key
         the parts from the third on are kept when the first of them is "visual_encoder" (actor_critic.net.visual_encoder.backbone... ->
@@ -236,23 +151,9 @@ class DepthEncoder(nn.Module):
         return enc
 
     # ---- compute ----
-    def _version(self) -> int:
-        return self.arena._version + sum(p._version for p, _, _, _ in self._views)
-
-    def refresh_weights(self):
-        """Rebuild the GEMM-ready weight copy from the fp32 arena (done automatically when a parameter's version counter moved)."""
-        check(self.L.etp_depth_refresh_weights(self.handle, _stream()), "etp_depth_refresh_weights")
-        self._packed_version = self._version()
-
     def _prepare(self, N: int):
         _require_gpu(self.arena, "DepthEncoder")
-        if self._version() != self._packed_version:
-            self.refresh_weights()
-        ws = self._ws.get(N)
-        if ws is None:
-            ws = torch.empty(int(self.L.etp_depth_ws_bytes(self.handle, N)), dtype=torch.uint8, device=self.arena.device)
-            self._ws[N] = ws
-        return ws, torch.empty(N, *self.output_shape, dtype=torch.float32, device=self.arena.device)
+        return self._scratch(N), torch.empty(N, *self.output_shape, dtype=torch.float32, device=self.arena.device)
 
     def _check_views(self, views):
         for v in views:

@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, ptr
+from .arena import build_tree, read_table
 
 
 def _cfg_get(config, name, default=None):
@@ -69,13 +70,6 @@ def make_c_config(config, dtype: torch.dtype) -> _lib.Config:
     return c
 
 
-class _Node(nn.Module):
-    """Plain container used to reproduce the reference's module tree (state-dict names)."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("container module; call the planner's forward_* methods")
-
-
 class Engine:
     """Owns the C planner handle, the flat arenas and the per-shape workspaces."""
 
@@ -86,13 +80,7 @@ class Engine:
         self.handle = self.L.etp_planner_create(ctypes.byref(cconf))
         if not self.handle:
             raise _lib.EtpError("etp_planner_create: " + self.L.etp_last_error().decode())
-        n = self.L.etp_planner_param_count(self.handle)
-        self.table = []
-        info = _lib.ParamInfo()
-        for i in range(n):
-            check(self.L.etp_planner_param_info(self.handle, i, ctypes.byref(info)), "param_info")
-            shape = tuple(int(info.shape[k]) for k in range(info.ndim))
-            self.table.append((info.name.decode(), shape, int(info.offset)))
+        self.table = read_table(self.L, "planner", self.handle, _lib.ParamInfo)
         self.total = int(self.L.etp_planner_arena_elems(self.handle))
         self.n_matrix = int(self.L.etp_planner_matrix_elems(self.handle))
         self.tdtype = torch.bfloat16 if cconf.dtype == _lib.ETP_BF16 else torch.float32
@@ -442,20 +430,7 @@ class GlocalTextPathNavCMT(nn.Module):
     # ---- parameter tree over the flat arena ---------------------------------------------------
     def _build_tree(self):
         eng = self._engine
-        self._views: List[tuple] = []
-        for name, shape, off in eng.table:
-            n = 1
-            for s in shape:
-                n *= s
-            p = nn.Parameter(eng.params[off:off + n].view(shape), requires_grad=True)
-            parts = name.split(".")
-            mod = self
-            for part in parts[:-1]:
-                if not hasattr(mod, part):
-                    mod.add_module(part, _Node())
-                mod = getattr(mod, part)
-            mod.register_parameter(parts[-1], p)
-            self._views.append((p, off, n, shape))
+        self._views: List[tuple] = build_tree(self, eng.params, eng.table, requires_grad=True)
         self._attach_grads(force=True)
 
     def _attach_grads(self, force: bool = False):

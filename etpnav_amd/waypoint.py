@@ -13,30 +13,24 @@ There is no CPU fallback: without the built library, or without a GPU, the compu
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from copy import deepcopy
-from typing import Dict, List, NamedTuple, Optional
+from functools import partial
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
-import torch.nn as nn
 
-from . import _lib
+from . import _lib, arena
 from ._lib import check, ptr
+from .arena import _edt, _stream
 
 NUM_ANGLES, NUM_IMGS, NUM_CLASSES = 120, 12, 12           # Policy_ViewSelection_ETP.py:176-178
 MAX_PREDICTIONS, NMS_SIGMA = 5, (7.0, 5.0)                # :233-236
 HEATMAP_OFFSET = 5                                        # TRM_net.py:20
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _require_gpu(t: torch.Tensor, what: str):
-    if t.device.type != "cuda":
-        raise _lib.EtpError(f"{what}: the waypoint kernels need an MI355X (cuda/hip device); no CPU fallback exists")
+_require_gpu = partial(arena._require_gpu, kernels="waypoint")
 
 
 # ---- operator level -----------------------------------------------------------------------------------------------------------
@@ -45,7 +39,7 @@ def ring_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ctx: torch.Tens
     """ctx[B*12, :768] = neighbourhood attention of q / k / v (rows [B*12, ld], 2-D tensors or column slices of one packed
     [B*12, 2304] buffer; stride(1) == 1).  Writes into `ctx` (same dtype, bf16 or fp32) and returns it."""
     _require_gpu(q, "ring_attn")
-    dt = {torch.float32: _lib.ETP_F32, torch.bfloat16: _lib.ETP_BF16}[q.dtype]
+    dt = _edt(q.dtype)
     for t in (q, k, v, ctx):
         assert t.dim() == 2 and t.stride(1) == 1 and t.dtype == q.dtype and t.device == q.device
     check(_lib.lib().etp_ring_attn_fwd(dt, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
@@ -100,33 +94,28 @@ def waypoint_tail(logits: torch.Tensor, max_pred: int = MAX_PREDICTIONS, sigma=N
 
 
 # ---- the predictor --------------------------------------------------------------------------------------------------------------
-class _Node(nn.Module):
-    """Plain container reproducing the reference's module tree (state-dict names)."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("container module; call BinaryDistPredictorTRM.forward")
+def _create(L, dtype):
+    h = L.etp_waypoint_create(_lib.ETP_BF16 if dtype == torch.bfloat16 else _lib.ETP_F32)
+    if not h:
+        raise _lib.EtpError("etp_waypoint_create: " + L.etp_last_error().decode())
+    return h
 
 
 def param_table(dtype: torch.dtype = torch.float32):
     """[(reference state-dict name, shape, arena offset)] of the engine; needs the built library, not a GPU."""
     L = _lib.lib()
-    h = L.etp_waypoint_create(_lib.ETP_BF16 if dtype == torch.bfloat16 else _lib.ETP_F32)
-    if not h:
-        raise _lib.EtpError("etp_waypoint_create: " + L.etp_last_error().decode())
+    h = _create(L, dtype)
     try:
-        info = _lib.ParamInfo()
-        out = []
-        for i in range(L.etp_waypoint_param_count(h)):
-            check(L.etp_waypoint_param_info(h, i, ctypes.byref(info)), "etp_waypoint_param_info")
-            out.append((info.name.decode(), tuple(int(info.shape[k]) for k in range(info.ndim)), int(info.offset)))
-        return out
+        return arena.read_table(L, "waypoint", h, _lib.ParamInfo)
     finally:
         L.etp_waypoint_destroy(h)
 
 
-class BinaryDistPredictorTRM(nn.Module):
+class BinaryDistPredictorTRM(arena.FrozenArenaModule):
     """TRM_net.py:9-88 on the HIP engine.  Parameters are views of one flat fp32 arena under the reference's names (the unused
     visual_merge / mergefeats_LayerNorm included), so ``load_state_dict(torch.load(cwp_fn)['predictor']['state_dict'])`` is strict."""
+
+    PREFIX, KIND = "waypoint", "predictor"
 
     def __init__(self, hidden_dim: int = 768, n_classes: int = 12, device=None, dtype: torch.dtype = torch.bfloat16):
         super().__init__()
@@ -134,73 +123,7 @@ class BinaryDistPredictorTRM(nn.Module):
         assert dtype in (torch.float32, torch.bfloat16)
         self.num_angles, self.num_imgs, self.n_classes = NUM_ANGLES, NUM_IMGS, NUM_CLASSES
         self.TRM_LAYER, self.TRM_NEIGHBOR, self.HEATMAP_OFFSET = 2, 1, HEATMAP_OFFSET
-        self.L = _lib.lib()
-        self.compute_dtype = dtype
-        self.handle = self.L.etp_waypoint_create(_lib.ETP_BF16 if dtype == torch.bfloat16 else _lib.ETP_F32)
-        if not self.handle:
-            raise _lib.EtpError("etp_waypoint_create: " + self.L.etp_last_error().decode())
-        info = _lib.ParamInfo()
-        self.table = []
-        for i in range(self.L.etp_waypoint_param_count(self.handle)):
-            check(self.L.etp_waypoint_param_info(self.handle, i, ctypes.byref(info)), "etp_waypoint_param_info")
-            self.table.append((info.name.decode(), tuple(int(info.shape[k]) for k in range(info.ndim)), int(info.offset)))
-        self.total = int(self.L.etp_waypoint_arena_elems(self.handle))
-        self.n_matrix = int(self.L.etp_waypoint_matrix_elems(self.handle))
-        dev = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
-        self.arena = torch.zeros(self.total, dtype=torch.float32, device=dev)
-        self.shadow = None
-        self._shadow_version = -1
-        self._ws: Dict[int, torch.Tensor] = {}
-        self._views: List[tuple] = []
-        for name, shape, off in self.table:
-            n = int(np.prod(shape))
-            p = nn.Parameter(self.arena[off:off + n].view(shape), requires_grad=False)
-            mod = self
-            parts = name.split(".")
-            for part in parts[:-1]:
-                if part not in mod._modules:
-                    mod.add_module(part, _Node())
-                mod = mod._modules[part]
-            mod.register_parameter(parts[-1], p)
-            self._views.append((p, off, n, shape))
-        self._bind()
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.L.etp_waypoint_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-    def _bind(self):
-        if self.arena.device.type != "cuda":
-            return
-        if self.compute_dtype == torch.bfloat16:
-            self.shadow = torch.zeros(self.n_matrix, dtype=torch.bfloat16, device=self.arena.device)
-        check(self.L.etp_waypoint_bind(self.handle, ptr(self.arena), ptr(self.shadow)), "etp_waypoint_bind")
-        self._shadow_version = -1
-
-    def _apply(self, fn, recurse=True):
-        new = fn(self.arena)
-        if new.dtype != torch.float32:
-            raise TypeError("the predictor's master parameters stay fp32; choose the compute dtype at construction")
-        if new.device != self.arena.device:
-            with torch.no_grad():
-                self.arena = new.contiguous()
-                for p, off, n, shape in self._views:
-                    p.data = self.arena[off:off + n].view(shape)
-                self._ws.clear()
-                self._bind()
-        return self
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        r = super().load_state_dict(state_dict, strict=strict, assign=False)
-        self._shadow_version = -1
-        return r
-
-    def _version(self) -> int:
-        return self.arena._version + sum(p._version for p, _, _, _ in self._views)
+        self._init_arena(_create(_lib.lib(), dtype), device, dtype)
 
     def forward(self, rgb_feats, depth_feats) -> torch.Tensor:
         """TRM_net.py:62-88.  depth_feats [12*B,128,4,4] (or [12*B,2048]); rgb_feats is ignored, as in the reference (only its
@@ -209,13 +132,7 @@ class BinaryDistPredictorTRM(nn.Module):
         x = depth_feats.reshape(depth_feats.shape[0], -1).to(device=self.arena.device, dtype=torch.float32).contiguous()
         assert x.shape[1] == 2048 and x.shape[0] % NUM_IMGS == 0, tuple(x.shape)
         B = x.shape[0] // NUM_IMGS
-        if self.shadow is not None and self._version() != self._shadow_version:
-            check(self.L.etp_waypoint_refresh_weights(self.handle, _stream()), "etp_waypoint_refresh_weights")
-            self._shadow_version = self._version()
-        ws = self._ws.get(B)
-        if ws is None:
-            ws = torch.empty(int(self.L.etp_waypoint_ws_bytes(self.handle, B)), dtype=torch.uint8, device=self.arena.device)
-            self._ws[B] = ws
+        ws = self._scratch(B)
         logits = torch.empty(B, NUM_ANGLES, NUM_CLASSES, dtype=torch.float32, device=self.arena.device)
         check(self.L.etp_waypoint_fwd(self.handle, ptr(x), B, ptr(logits), ptr(ws), _stream()), "etp_waypoint_fwd")
         return logits

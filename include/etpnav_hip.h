@@ -613,11 +613,14 @@ int etp_quick_gelu(int dtype, void* x, int64_t n, etp_stream_t stream);
 int etp_clip_cls_ln(int dtype, const float* x, const float* gamma, const float* beta, void* out, int N, int S, float eps,
                     etp_stream_t stream);
 
-typedef struct etp_clip_tensor_info {
-  char name[128];                        /* key of OpenAI CLIP's state dict without the leading "visual." */
+/* One parameter of a frozen encoder (rank <= 4).  name: CLIP: key of OpenAI CLIP's state dict without the leading "visual.";
+ * depth: key of VlnResnetDepthEncoder.visual_encoder's state dict. */
+typedef struct etp_tensor_info {
+  char name[128];
   int32_t ndim; int64_t shape[4];
-  int64_t offset;                        /* element offset in the fp32 arena (and, for the matrices, in the bf16 shadow) */
-} etp_clip_tensor_info;
+  int64_t offset;                        /* element offset in the fp32 arena (and, for the matrices, in the bf16 shadow / packed copy) */
+} etp_tensor_info;
+typedef etp_tensor_info etp_clip_tensor_info;
 
 typedef struct etp_clip etp_clip;
 /* dtype ETP_F32 | ETP_BF16 (GEMM / attention operand precision; the residual stream and the LayerNorms are fp32 in both);
@@ -682,11 +685,7 @@ int etp_maxpool3x3s2(int dtype, const void* x, void* out, int N, int H, int W, i
  * downsample.  C a multiple of 8. */
 int etp_conv_rows(int dtype, const void* x, void* out, int N, int H, int W, int C, int k, int stride, etp_stream_t stream);
 
-typedef struct etp_depth_tensor_info {
-  char name[128];                        /* key of VlnResnetDepthEncoder.visual_encoder's state dict */
-  int32_t ndim; int64_t shape[4];
-  int64_t offset;                        /* element offset in the fp32 arena (and, for the matrices, in the packed copy) */
-} etp_depth_tensor_info;
+typedef etp_tensor_info etp_depth_tensor_info;
 
 typedef struct etp_depth etp_depth;
 /* dtype ETP_F32 | ETP_BF16 (GEMM operand and activation precision; every product and every GroupNorm computes in fp32); image_size a
