@@ -20,6 +20,7 @@ counter-based generator that the backward recomputes); ``model.eval()`` makes th
 from __future__ import annotations
 
 import ctypes
+from contextlib import contextmanager
 from types import SimpleNamespace
 from typing import Dict, List, Optional
 
@@ -35,6 +36,14 @@ def _cfg_get(config, name, default=None):
     if isinstance(config, dict):
         return config.get(name, default)
     return getattr(config, name, default)
+
+
+def config_dropout_rates(config):
+    """(p_hidden, p_attn, p_head) of a model config, the reference's defaults where it names none"""
+    return tuple(float(_cfg_get(config, k, 0.1)) for k in ("hidden_dropout_prob", "attention_probs_dropout_prob", "pred_head_dropout_prob"))
+
+
+_KEEP = object()                        # Engine.scope: "leave this mode as it is"
 
 
 def make_c_config(config, dtype: torch.dtype) -> _lib.Config:
@@ -146,6 +155,40 @@ class Engine:
         ph, pa, pd, pe, seed = drop
         check(self.L.etp_planner_set_dropout(self.handle, ph, pa, pd, pe, seed), "set_dropout")
 
+    @contextmanager
+    def scope(self, aux=_KEEP, aux2=_KEEP, lazy=_KEEP, grad_overwrite=_KEEP, drop=_KEEP):
+        """The one place the handle's modes are set.  The handle is shared by every user of a model (the autograd bridges, each
+        cached PlannerStep, MlmStep), so whoever enqueues installs what it needs first: side streams (`aux`: weight-gradient
+        GEMMs, `aux2`: the d txt_embeds chain of etp_nav_bwd), the lazy-join level, the dropout state `drop` (as set_dropout) and
+        the gradient-overwrite mode.  An argument left out is not touched.  On exit, exceptions included, grad_overwrite is back
+        at 0 -- it never leaks to the next user; streams, lazy level and dropout stay installed (join_aux below relies on seeing
+        the aux stream the last step installed)."""
+        L, h = self.L, self.handle
+        if aux is not _KEEP:
+            check(L.etp_planner_set_aux_stream(h, aux), "set_aux_stream")
+        if aux2 is not _KEEP:
+            check(L.etp_planner_set_aux2_stream(h, aux2), "set_aux2_stream")
+        if lazy is not _KEEP:
+            check(L.etp_planner_set_lazy_join(h, lazy), "set_lazy_join")
+        if drop is not _KEEP:
+            self.set_dropout(drop)
+        if grad_overwrite is not _KEEP:
+            check(L.etp_planner_set_grad_overwrite(h, int(grad_overwrite)), "set_grad_overwrite")
+        try:
+            yield
+        finally:
+            if grad_overwrite is not _KEEP:
+                check(L.etp_planner_set_grad_overwrite(h, 0), "set_grad_overwrite")
+
+    def release_aux(self):
+        """take the aux stream off the handle (its owner is done with it or about to destroy it)"""
+        check(self.L.etp_planner_set_aux_stream(self.handle, None), "set_aux_stream")
+
+    def join_aux(self):
+        """A PlannerStep sharing this planner may have switched on lazy joins of the weight-gradient stream: autograd consumers
+        read .grad right after backward, so the bridges join here (no-op without an aux stream)."""
+        check(self.L.etp_planner_join_aux(self.handle, self.stream()), "join_aux")
+
     def buf(self, nbytes: int) -> torch.Tensor:
         return torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
 
@@ -165,10 +208,10 @@ class _TxtFn(torch.autograd.Function):
         H = eng.cconf.hidden
         out = torch.empty(B, L, H, dtype=torch.float32, device=eng.device)
         stash = eng.buf(eng.L.etp_txt_stash_bytes(eng.handle, B, L))
-        eng.set_dropout(drop)
         ctx.drop = drop
-        check(eng.L.etp_txt_fwd(eng.handle, ptr(txt_ids), ptr(txt_masks), B, L, ptr(out), ptr(stash), eng.stream()),
-              "etp_txt_fwd")
+        with eng.scope(drop=drop):
+            check(eng.L.etp_txt_fwd(eng.handle, ptr(txt_ids), ptr(txt_masks), B, L, ptr(out), ptr(stash), eng.stream()),
+                  "etp_txt_fwd")
         ctx.eng, ctx.stash, ctx.dims = eng, stash, (B, L)
         ctx.save_for_backward(txt_ids, txt_masks)
         return out
@@ -179,9 +222,9 @@ class _TxtFn(torch.autograd.Function):
         txt_ids, txt_masks = ctx.saved_tensors
         dout = dout.float().contiguous()
         ws = eng.ws(("txt", B, L), eng.L.etp_txt_ws_bytes(eng.handle, B, L))
-        eng.set_dropout(ctx.drop)
-        check(eng.L.etp_txt_bwd(eng.handle, ptr(dout), ptr(txt_ids), ptr(txt_masks), B, L, ptr(ctx.stash), ptr(ws),
-                                eng.stream()), "etp_txt_bwd")
+        with eng.scope(drop=ctx.drop):
+            check(eng.L.etp_txt_bwd(eng.handle, ptr(dout), ptr(txt_ids), ptr(txt_masks), B, L, ptr(ctx.stash), ptr(ws),
+                                    eng.stream()), "etp_txt_bwd")
         return None, None, None, None, None
 
 
@@ -190,13 +233,13 @@ class _PanoFn(torch.autograd.Function):
     def forward(ctx, anchor, eng: Engine, drop, rgb, dep, loc, nav_types, view_lens):
         B, V, _ = rgb.shape
         H = eng.cconf.hidden
-        eng.set_dropout(drop)
         ctx.drop = drop
         out = torch.empty(B, V, H, dtype=torch.float32, device=eng.device)
         masks = torch.empty(B, V, dtype=torch.bool, device=eng.device)
         stash = eng.buf(eng.L.etp_pano_stash_bytes(eng.handle, B, V))
-        check(eng.L.etp_pano_fwd(eng.handle, ptr(rgb), ptr(dep), ptr(loc), ptr(nav_types), ptr(view_lens), B, V, ptr(out),
-                                 ptr(masks), ptr(stash), eng.stream()), "etp_pano_fwd")
+        with eng.scope(drop=drop):
+            check(eng.L.etp_pano_fwd(eng.handle, ptr(rgb), ptr(dep), ptr(loc), ptr(nav_types), ptr(view_lens), B, V, ptr(out),
+                                     ptr(masks), ptr(stash), eng.stream()), "etp_pano_fwd")
         ctx.eng, ctx.stash, ctx.dims = eng, stash, (B, V)
         ctx.need_rgb_grad = rgb.requires_grad
         ctx.save_for_backward(rgb, dep, loc, nav_types)
@@ -210,12 +253,10 @@ class _PanoFn(torch.autograd.Function):
         dout = dout.float().contiguous()
         d_rgb = torch.empty(B, V, eng.cconf.img_feat, dtype=torch.float32, device=eng.device) if ctx.need_rgb_grad else None
         ws = eng.ws(("pano", B, V), eng.L.etp_pano_ws_bytes(eng.handle, B, V))
-        eng.set_dropout(ctx.drop)
-        check(eng.L.etp_pano_bwd(eng.handle, ptr(dout), ptr(rgb), ptr(dep), ptr(loc), ptr(nav_types), B, V, ptr(d_rgb),
-                                 ptr(ctx.stash), ptr(ws), eng.stream()), "etp_pano_bwd")
-        # a PlannerStep sharing this planner may have switched on lazy joins of the weight-gradient stream: autograd
-        # consumers read .grad right after backward, so join here (no-op without an aux stream)
-        check(eng.L.etp_planner_join_aux(eng.handle, eng.stream()), "join_aux")
+        with eng.scope(drop=ctx.drop):
+            check(eng.L.etp_pano_bwd(eng.handle, ptr(dout), ptr(rgb), ptr(dep), ptr(loc), ptr(nav_types), B, V, ptr(d_rgb),
+                                     ptr(ctx.stash), ptr(ws), eng.stream()), "etp_pano_bwd")
+        eng.join_aux()
         return None, None, None, d_rgb, None, None, None, None
 
 
@@ -223,15 +264,15 @@ class _NavFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, eng: Engine, drop, txt_embeds, txt_masks, step_ids, img_fts, pos_fts, gmasks, visited, dists):
         B, L, H = txt_embeds.shape
-        eng.set_dropout(drop)
         ctx.drop = drop
         G = step_ids.shape[1]
         out = torch.empty(B, G, H, dtype=torch.float32, device=eng.device)
         logits = torch.empty(B, G, dtype=torch.float32, device=eng.device)
         stash = eng.buf(eng.L.etp_nav_stash_bytes(eng.handle, B, L, G))
-        check(eng.L.etp_nav_fwd(eng.handle, ptr(txt_embeds), ptr(txt_masks), ptr(step_ids), ptr(img_fts), ptr(pos_fts),
-                                ptr(gmasks), ptr(visited), ptr(dists), B, L, G, ptr(out), ptr(logits), ptr(stash),
-                                eng.stream()), "etp_nav_fwd")
+        with eng.scope(drop=drop):
+            check(eng.L.etp_nav_fwd(eng.handle, ptr(txt_embeds), ptr(txt_masks), ptr(step_ids), ptr(img_fts), ptr(pos_fts),
+                                    ptr(gmasks), ptr(visited), ptr(dists), B, L, G, ptr(out), ptr(logits), ptr(stash),
+                                    eng.stream()), "etp_nav_fwd")
         ctx.eng, ctx.stash, ctx.dims = eng, stash, (B, L, G)
         ctx.save_for_backward(txt_embeds, txt_masks, step_ids, pos_fts, gmasks, visited, dists)
         return out, logits
@@ -246,13 +287,11 @@ class _NavFn(torch.autograd.Function):
         d_txt = torch.empty(B, L, H, dtype=torch.float32, device=eng.device)
         d_img = torch.empty(B, G, H, dtype=torch.float32, device=eng.device)
         ws = eng.ws(("nav", B, L, G), eng.L.etp_nav_ws_bytes(eng.handle, B, L, G))
-        eng.set_dropout(ctx.drop)
-        check(eng.L.etp_nav_bwd(eng.handle, ptr(d_out), ptr(d_logits), ptr(txt_embeds), ptr(txt_masks),
-                                ptr(step_ids), ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, ptr(d_txt),
-                                ptr(d_img), ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd")
-        # a PlannerStep sharing this planner may have switched on lazy joins of the weight-gradient stream: autograd
-        # consumers read .grad right after backward, so join here (no-op without an aux stream)
-        check(eng.L.etp_planner_join_aux(eng.handle, eng.stream()), "join_aux")
+        with eng.scope(drop=ctx.drop):
+            check(eng.L.etp_nav_bwd(eng.handle, ptr(d_out), ptr(d_logits), ptr(txt_embeds), ptr(txt_masks),
+                                    ptr(step_ids), ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, ptr(d_txt),
+                                    ptr(d_img), ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd")
+        eng.join_aux()
         return None, None, None, d_txt, None, None, d_img, None, None, None, None
 
 
@@ -325,19 +364,19 @@ class _NavCachedFn(torch.autograd.Function):
         H = eng.cconf.hidden
         Bt = B // steps_T
         cache = ctypes.c_void_p(kv.data_ptr() - int(eng.L.etp_nav_kv_offset(eng.handle, Bt, L)))   # base of the cache buffer
-        eng.set_dropout(drop)
         ctx.drop = drop
         out = torch.empty(B, G, H, dtype=torch.float32, device=eng.device)
         logits = torch.empty(B, G, dtype=torch.float32, device=eng.device)
         stash = eng.buf(eng.L.etp_nav_stash_bytes(eng.handle, B, L, G))
-        if steps_T > 1:
-            check(eng.L.etp_nav_fwd_kv_steps(eng.handle, cache, ptr(txt_masks), ptr(step_ids), ptr(img_fts), ptr(pos_fts), ptr(gmasks),
-                                             ptr(visited), ptr(dists), B, L, G, Bt, ptr(out), ptr(logits), ptr(stash), eng.stream()),
-                  "etp_nav_fwd_kv_steps")
-        else:
-            check(eng.L.etp_nav_fwd_kv(eng.handle, cache, ptr(txt_masks), ptr(step_ids), ptr(img_fts), ptr(pos_fts), ptr(gmasks),
-                                       ptr(visited), ptr(dists), B, L, G, ptr(out), ptr(logits), ptr(stash), eng.stream()),
-                  "etp_nav_fwd_kv")
+        with eng.scope(drop=drop):
+            if steps_T > 1:
+                check(eng.L.etp_nav_fwd_kv_steps(eng.handle, cache, ptr(txt_masks), ptr(step_ids), ptr(img_fts), ptr(pos_fts), ptr(gmasks),
+                                                 ptr(visited), ptr(dists), B, L, G, Bt, ptr(out), ptr(logits), ptr(stash), eng.stream()),
+                      "etp_nav_fwd_kv_steps")
+            else:
+                check(eng.L.etp_nav_fwd_kv(eng.handle, cache, ptr(txt_masks), ptr(step_ids), ptr(img_fts), ptr(pos_fts), ptr(gmasks),
+                                           ptr(visited), ptr(dists), B, L, G, ptr(out), ptr(logits), ptr(stash), eng.stream()),
+                      "etp_nav_fwd_kv")
         ctx.eng, ctx.stash, ctx.dims, ctx.cache, ctx.kv_shape, ctx.steps_T = eng, stash, (B, L, G), cache, kv.shape, steps_T
         ctx.save_for_backward(txt_masks, step_ids, pos_fts, gmasks, visited, dists, kv)
         return out, logits
@@ -352,25 +391,23 @@ class _NavCachedFn(torch.autograd.Function):
         d_kv = torch.empty(ctx.kv_shape, dtype=eng.tdtype, device=eng.device)
         d_img = torch.empty(B, G, H, dtype=torch.float32, device=eng.device)
         ws = eng.ws(("nav", B, L, G), eng.L.etp_nav_ws_bytes(eng.handle, B, L, G))
-        eng.set_dropout(ctx.drop)
-        if T > 1 and eng.L.etp_nav_kv_steps_mode(eng.handle, B, L, G, B // T) == 2:
-            check(eng.L.etp_nav_bwd_kv_steps_sum(eng.handle, ptr(d_out), ptr(d_logits), ctx.cache, ptr(txt_masks), ptr(step_ids),
-                                                 ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, B // T, ptr(d_kv),
-                                                 ptr(d_img), ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd_kv_steps_sum")
-        elif T > 1:
-            n_x, _, H2 = ctx.kv_shape
-            d_kv_steps = torch.empty(n_x, B * L, H2, dtype=eng.tdtype, device=eng.device)
-            check(eng.L.etp_nav_bwd_kv_steps(eng.handle, ptr(d_out), ptr(d_logits), ctx.cache, ptr(txt_masks), ptr(step_ids),
-                                             ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, B // T, ptr(d_kv_steps),
-                                             ptr(d_img), ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd_kv_steps")
-            check(eng.L.etp_nav_kv_sum_steps(eng.handle, ptr(d_kv_steps), B // T, L, T, ptr(d_kv), eng.stream()), "etp_nav_kv_sum_steps")
-        else:
-            check(eng.L.etp_nav_bwd_kv(eng.handle, ptr(d_out), ptr(d_logits), ctx.cache, ptr(txt_masks), ptr(step_ids),
-                                       ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, ptr(d_kv), ptr(d_img),
-                                       ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd_kv")
-        # a PlannerStep sharing this planner may have switched on lazy joins of the weight-gradient stream: autograd
-        # consumers read .grad right after backward, so join here (no-op without an aux stream)
-        check(eng.L.etp_planner_join_aux(eng.handle, eng.stream()), "join_aux")
+        with eng.scope(drop=ctx.drop):
+            if T > 1 and eng.L.etp_nav_kv_steps_mode(eng.handle, B, L, G, B // T) == 2:
+                check(eng.L.etp_nav_bwd_kv_steps_sum(eng.handle, ptr(d_out), ptr(d_logits), ctx.cache, ptr(txt_masks), ptr(step_ids),
+                                                     ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, B // T, ptr(d_kv),
+                                                     ptr(d_img), ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd_kv_steps_sum")
+            elif T > 1:
+                n_x, _, H2 = ctx.kv_shape
+                d_kv_steps = torch.empty(n_x, B * L, H2, dtype=eng.tdtype, device=eng.device)
+                check(eng.L.etp_nav_bwd_kv_steps(eng.handle, ptr(d_out), ptr(d_logits), ctx.cache, ptr(txt_masks), ptr(step_ids),
+                                                 ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, B // T, ptr(d_kv_steps),
+                                                 ptr(d_img), ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd_kv_steps")
+                check(eng.L.etp_nav_kv_sum_steps(eng.handle, ptr(d_kv_steps), B // T, L, T, ptr(d_kv), eng.stream()), "etp_nav_kv_sum_steps")
+            else:
+                check(eng.L.etp_nav_bwd_kv(eng.handle, ptr(d_out), ptr(d_logits), ctx.cache, ptr(txt_masks), ptr(step_ids),
+                                           ptr(pos_fts), ptr(gmasks), ptr(visited), ptr(dists), B, L, G, ptr(d_kv), ptr(d_img),
+                                           ptr(ctx.stash), ptr(ws), eng.stream()), "etp_nav_bwd_kv")
+        eng.join_aux()
         return None, None, None, d_kv, None, None, None, d_img, None, None, None, None, None
 
 
@@ -417,10 +454,7 @@ class GlocalTextPathNavCMT(nn.Module):
     def _dropout(self):
         if not self.training:
             return None
-        c = self.config
-        ph = float(_cfg_get(c, "hidden_dropout_prob", 0.1))
-        pa = float(_cfg_get(c, "attention_probs_dropout_prob", 0.1))
-        pd = float(_cfg_get(c, "pred_head_dropout_prob", 0.1))
+        ph, pa, pd = config_dropout_rates(self.config)
         pe = float(self.drop_env_prob)
         if ph == 0.0 and pa == 0.0 and pd == 0.0 and pe == 0.0:
             return None

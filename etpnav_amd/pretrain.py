@@ -15,46 +15,25 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .graph_inputs import pack_traj_csr
 from .planner import GlocalTextPathNavCMT
+from .step import N_MLM_INPUTS, _Staging, _destroy_streams, _new_stream
 
 
-class MlmStep:
+class MlmStep(_Staging):
     def __init__(self, model: GlocalTextPathNavCMT, batch: Dict[str, torch.Tensor], dropout=None, drop_seed: int = 0,
                  overlap: bool = True):
         """batch: etpnav_amd.synthetic.make_sap_batch layout + ``txt_labels`` [B,L] (-1 = not masked, else the token id).
+        dropout: None, "config" (the model config's rates; no drop_env in this task) or (p_hidden, p_attn, p_head, p_env).
         overlap: the three-stream schedule of PlannerStep -- weight gradients on an `aux` stream, the panorama branch
         (forward and backward) on `s2` beside the text branch; False = everything on the caller's stream."""
-        eng = self.eng = model._engine
-        eng.require_gpu()
-        if not eng.cconf.use_lang2visn:
+        if not model._engine.cconf.use_lang2visn:
             raise _lib.EtpError("the MLM task needs a model built with use_lang2visn_attn=True (pre-training config)")
-        self.model, self.L = model, eng.L
-        dev = eng.device
-        if dropout == "config":
-            c = model.config
-            g = lambda k: float(c[k] if isinstance(c, dict) and k in c else getattr(c, k, 0.1))
-            dropout = (g("hidden_dropout_prob"), g("attention_probs_dropout_prob"), g("pred_head_dropout_prob"), 0.0)
-        self.dropout, self.drop_seed, self.step_no = dropout, int(drop_seed) & 0xFFFFFFFF, 0
+        self._stage(model, batch, N_MLM_INPUTS, dropout, drop_seed, 0.0)
         # gradient accumulation (PretrainDriver): later micro-steps keep the arena (zero_grads False) and every micro-step's mean
         # loss is scaled by 1 / accumulation steps (train_r2r.py:250-252)
         self.zero_grads, self.loss_scale = True, 1.0
-        B, Lt = batch["txt_ids"].shape
-        Bp, V = batch["rgb_fts"].shape[:2]
-        G = batch["gmap_step_ids"].shape[1]
-        H = eng.cconf.hidden
-        self.dims = (B, Lt, Bp, V, G, H)
-        mv = lambda x, dt=None: (x.to(dt) if dt is not None else x).contiguous().to(dev)
-        self.inp = {
-            "txt_ids": mv(batch["txt_ids"], torch.int64), "txt_masks": mv(batch["txt_masks"], torch.bool),
-            "rgb": mv(batch["rgb_fts"], torch.float32), "dep": mv(batch["dep_fts"], torch.float32),
-            "loc": mv(batch["loc_fts"], torch.float32), "nav": mv(batch["nav_types"], torch.int64),
-            "view_lens": mv(batch["view_lens"], torch.int64), "step_ids": mv(batch["gmap_step_ids"], torch.int64),
-            "pos": mv(batch["gmap_pos_fts"], torch.float32), "gmask": mv(batch["gmap_masks"], torch.bool),
-        }
-        tr = batch["traj"]
-        fwd, bwd = pack_traj_csr(tr["traj_vp_lens"], tr["traj_vpids"], tr["traj_cand_vpids"], tr["gmap_vpids"], V, G)
-        self.csr_f, self.csr_b = tuple(x.to(dev) for x in fwd), tuple(x.to(dev) for x in bwd)
+        eng, dev, (B, Lt, G) = self.eng, self.eng.device, (self.B, self.Lt, self.G)
+        self.dims = (B, Lt, self.Bp, self.V, G, eng.cconf.hidden)
         # masked positions: row gather of the text (and its transpose for the backward)
         sel = (batch["txt_labels"] != -1).reshape(-1)
         rows = torch.nonzero(sel).reshape(-1).to(torch.int32)
@@ -66,22 +45,10 @@ class MlmStep:
         ptr_t = torch.zeros(B * Lt + 1, dtype=torch.int32)
         ptr_t[1:] = torch.cumsum(sel.to(torch.int32), 0)
         self.selT = (ptr_t.to(dev), i32(torch.arange(Nm)), torch.ones(Nm, dtype=torch.float32, device=dev))
-        self.labels = mv(batch["txt_labels"].reshape(-1)[sel], torch.int64)
-        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
-        self.txt, self.pano, self.pmask = e(B, Lt, H), e(Bp, V, H), e(Bp, V, dt=torch.bool)
-        self.gimg, self.loss = e(B, G, H), torch.zeros(1, dtype=torch.float32, device=dev)
-        self.d_txt, self.d_gimg, self.d_pano = e(B, Lt, H), e(B, G, H), e(Bp, V, H)
-        h = eng.handle
-        self.st_txt = eng.buf(self.L.etp_txt_stash_bytes(h, B, Lt)); self.ws_txt = eng.buf(self.L.etp_txt_ws_bytes(h, B, Lt))
-        self.st_pano = eng.buf(self.L.etp_pano_stash_bytes(h, Bp, V)); self.ws_pano = eng.buf(self.L.etp_pano_ws_bytes(h, Bp, V))
-        self.st_mlm = eng.buf(self.L.etp_mlm_stash_bytes(h, B, Lt, G, Nm)); self.ws_mlm = eng.buf(self.L.etp_mlm_ws_bytes(h, B, Lt, G, Nm))
-        self.aux = self.s2 = None
-        if overlap:
-            import ctypes
-            a, b2 = ctypes.c_void_p(), ctypes.c_void_p()
-            check(self.L.etp_stream_create(ctypes.byref(a)), "stream_create")
-            check(self.L.etp_stream_create(ctypes.byref(b2)), "stream_create")
-            self.aux, self.s2 = a.value, b2.value
+        self.labels = batch["txt_labels"].reshape(-1)[sel].to(torch.int64).contiguous().to(dev)
+        self.st_mlm = eng.buf(self.L.etp_mlm_stash_bytes(eng.handle, B, Lt, G, Nm))
+        self.ws_mlm = eng.buf(self.L.etp_mlm_ws_bytes(eng.handle, B, Lt, G, Nm))
+        self.aux, self.s2 = (_new_stream(self.L), _new_stream(self.L)) if overlap else (None, None)
 
     @staticmethod
     def batch_shape_key(batch):
@@ -90,60 +57,51 @@ class MlmStep:
         return (B, Lt, Bp, V, batch["gmap_step_ids"].shape[1], int((batch["txt_labels"] != -1).sum()))
 
     def shape_key(self):
-        B, Lt, Bp, V, G, _ = self.dims
-        return (B, Lt, Bp, V, G, self.Nm)
+        return (self.B, self.Lt, self.Bp, self.V, self.G, self.Nm)
 
     def close(self):
-        self.L.etp_planner_set_aux_stream(self.eng.handle, None)
-        for st in (self.aux, self.s2):
-            if st is not None:
-                self.L.etp_stream_destroy(st)
+        self.eng.release_aux()
+        _destroy_streams(self.L, self.aux, self.s2)
         self.aux = self.s2 = None
 
     def run_eager(self, backward: bool = True):
-        L, eng, i = self.L, self.eng, self.inp
-        h, s = eng.handle, eng.stream()
-        s2 = self.s2 if self.s2 is not None else s
-        B, Lt, Bp, V, G, H = self.dims
         self.step_no += 1
-        eng.set_dropout(None if self.dropout is None else
-                        tuple(self.dropout) + ((self.drop_seed << 32) | (self.step_no & 0xFFFFFFFF),))
-        check(L.etp_planner_set_aux_stream(h, self.aux), "set_aux_stream")
-        check(L.etp_planner_set_aux2_stream(h, None), "set_aux2_stream")
-        check(L.etp_planner_set_lazy_join(h, 0), "set_lazy_join")      # (PlannerStep re-installs its own streams at every enqueue)
+        try:       # no lazy joins, no d_txt stream (PlannerStep re-installs its own at every enqueue)
+            with self.eng.scope(aux=self.aux, aux2=None, lazy=0, drop=self._drop_state()):
+                self._enqueue(self.eng.stream(), backward)
+        finally:   # the aux stream is this step's own: off the handle on every exit
+            self.eng.release_aux()
+
+    def _enqueue(self, s: int, backward: bool):
+        L, h, i = self.L, self.eng.handle, self.inp
+        s2 = self.s2 if self.s2 is not None else s
+        B, Lt, G, Nm = self.B, self.Lt, self.G, self.Nm
         # text weights first on the main stream; everything else (panorama / x-layer casts, the gradient memset) rides on the
         # panorama stream, whose join precedes the MLM forward and every backward kernel
         check(L.etp_planner_refresh_part(h, 0, s), "refresh text weights")
         check(L.etp_memset_async(ptr(self.loss), 0, 4, s), "memset loss")
         check(L.etp_stream_after(s, s2), "fork")
-        check(L.etp_planner_refresh_part(h, 1, s2), "refresh panorama weights")
-        check(L.etp_planner_refresh_part(h, 2, s2), "refresh navigation weights")
+        self._refresh_side_weights(s2)
         if backward and self.zero_grads:
-            check(L.etp_memset_async(ptr(eng.grads), 0, eng.grads.numel() * 4, s2), "memset grads")
-        check(L.etp_txt_fwd(h, ptr(i["txt_ids"]), ptr(i["txt_masks"]), B, Lt, ptr(self.txt), ptr(self.st_txt), s), "txt_fwd")
-        check(L.etp_pano_fwd(h, ptr(i["rgb"]), ptr(i["dep"]), ptr(i["loc"]), ptr(i["nav"]), ptr(i["view_lens"]), Bp, V,
-                             ptr(self.pano), ptr(self.pmask), ptr(self.st_pano), s2), "pano_fwd")
+            check(L.etp_memset_async(ptr(self.eng.grads), 0, self.eng.grads.numel() * 4, s2), "memset grads")
+        self._txt_fwd(s)
+        self._pano_fwd(s2)
         check(L.etp_stream_after(s2, s), "join")
-        pf, xf, wf = self.csr_f
-        check(L.etp_gather_sum(_lib.ETP_F32, ptr(self.pano), ptr(pf), ptr(xf), ptr(wf), ptr(self.gimg), B * G, H, 0, s), "aggregate")
+        self._assemble(s)
         check(L.etp_mlm_fwd(h, ptr(self.txt), ptr(i["txt_masks"]), ptr(i["step_ids"]), ptr(self.gimg), ptr(i["pos"]),
                             ptr(i["gmask"]), ptr(self.sel[0]), ptr(self.sel[1]), ptr(self.sel[2]), ptr(self.labels), B, Lt, G,
-                            self.Nm, self.loss_scale / self.Nm, ptr(self.loss), ptr(self.st_mlm), s), "mlm_fwd")
+                            Nm, self.loss_scale / Nm, ptr(self.loss), ptr(self.st_mlm), s), "mlm_fwd")
         if not backward:
             return
         check(L.etp_mlm_bwd(h, ptr(self.txt), ptr(i["txt_masks"]), ptr(i["step_ids"]), ptr(i["pos"]), ptr(i["gmask"]),
-                            ptr(self.selT[0]), ptr(self.selT[1]), ptr(self.selT[2]), B, Lt, G, self.Nm, ptr(self.d_txt),
+                            ptr(self.selT[0]), ptr(self.selT[1]), ptr(self.selT[2]), B, Lt, G, Nm, ptr(self.d_txt),
                             ptr(self.d_gimg), ptr(self.st_mlm), ptr(self.ws_mlm), s), "mlm_bwd")
-        pb, xb, wb = self.csr_b
-        check(L.etp_gather_sum(_lib.ETP_F32, ptr(self.d_gimg), ptr(pb), ptr(xb), ptr(wb), ptr(self.d_pano), Bp * V, H, 0, s),
-              "aggregate bwd")
+        self._assemble_bwd(s)
         check(L.etp_stream_after(s, s2), "fork")                  # panorama backward beside the text backward
-        check(L.etp_pano_bwd(h, ptr(self.d_pano), ptr(i["rgb"]), ptr(i["dep"]), ptr(i["loc"]), ptr(i["nav"]), Bp, V, None,
-                             ptr(self.st_pano), ptr(self.ws_pano), s2), "pano_bwd")
+        self._pano_bwd(s2)
         check(L.etp_txt_bwd(h, ptr(self.d_txt), ptr(i["txt_ids"]), ptr(i["txt_masks"]), B, Lt, ptr(self.st_txt), ptr(self.ws_txt),
                             s), "txt_bwd")
         check(L.etp_stream_after(s2, s), "join")
-        check(L.etp_planner_set_aux_stream(h, None), "set_aux_stream")
 
 
 # ---- multi-task driver pieces (what pretrain_src/pretrain_src/data/loader.py:18-75 and train_r2r.py:229-300 provide) -------------

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .planner import GlocalTextPathNavCMT
+from .planner import GlocalTextPathNavCMT, _cfg_get, config_dropout_rates
 
 
 def build_node_csr(view_lens: torch.Tensor, V: int, G: int):
@@ -50,27 +50,124 @@ def build_node_csr(view_lens: torch.Tensor, V: int, G: int):
     return (i32(ptr_f), i32(idx_f), f32(w_f)), (i32(ptr_b), i32(idx_b), f32(w_b))
 
 
-def _side_stream(L, level: int):
-    """leaf stream (weight gradients / the panorama branch) at the lowest priority.  (Confining these streams to a slice of the
-    chip with hipExtStreamCreateWithCUMask was measured 1.8x SLOWER -- 7.8 ms per step whatever the share,
-    profiles/r03_ab_runs.json group c4 -- and is not offered.)"""
+def _new_stream(L, prio: Optional[int] = None):
+    """A stream at the default priority, or (`prio`) at the given level: -1 = lowest, for leaf work (weight gradients / the panorama
+    branch).  (Confining these streams to a slice of the chip with hipExtStreamCreateWithCUMask was measured 1.8x SLOWER -- 7.8 ms
+    per step whatever the share, profiles/r03_ab_runs.json group c4 -- and is not offered.)"""
     h = ctypes.c_void_p()
-    check(L.etp_stream_create_prio(ctypes.byref(h), level), "stream_create")
+    if prio is None:
+        check(L.etp_stream_create(ctypes.byref(h)), "stream_create")
+    else:
+        check(L.etp_stream_create_prio(ctypes.byref(h), prio), "stream_create")
     return h.value
 
 
-class PlannerStep:
+def _destroy_streams(L, *streams):
+    for st in streams:
+        if st is not None:
+            L.etp_stream_destroy(st)
+
+
+def _node_csr(batch, V: int, G: int, dev):
+    """The node aggregation's CSR and its transpose on the device: from the trajectory lists (batch['traj']: one panorama per
+    trajectory step, the pre-training tasks, pretrain_cmt.py:223-283) or one panorama per episode (the fine-tuning rollout step)."""
+    if "traj" in batch:
+        from .graph_inputs import pack_traj_csr
+        tr = batch["traj"]
+        f, b = pack_traj_csr(tr["traj_vp_lens"], tr["traj_vpids"], tr["traj_cand_vpids"], tr["gmap_vpids"], V, G)
+    else:
+        if batch["rgb_fts"].shape[0] != batch["txt_ids"].shape[0]:
+            raise ValueError("rgb_fts batch differs from txt_ids batch: pass the trajectory lists as batch['traj']")
+        f, b = build_node_csr(batch["view_lens"].cpu(), V, G)
+    return tuple(x.to(dev) for x in f), tuple(x.to(dev) for x in b)
+
+
+# (inp key, batch key, dtype) of every device input of a step; MlmStep stages the first N_MLM_INPUTS of them
+INPUTS = (("txt_ids", "txt_ids", torch.int64), ("txt_masks", "txt_masks", torch.bool), ("rgb", "rgb_fts", torch.float32),
+          ("dep", "dep_fts", torch.float32), ("loc", "loc_fts", torch.float32), ("nav", "nav_types", torch.int64),
+          ("view_lens", "view_lens", torch.int64), ("step_ids", "gmap_step_ids", torch.int64), ("pos", "gmap_pos_fts", torch.float32),
+          ("gmask", "gmap_masks", torch.bool),
+          ("visited", "gmap_visited_masks", torch.bool), ("dists", "gmap_pair_dists", torch.float32), ("labels", "labels", torch.int64))
+N_MLM_INPUTS = 10
+
+
+class _Staging:
+    """What PlannerStep and MlmStep (pretrain.py) stage alike -- device inputs, node CSR, the API tensors and stash / workspace of the
+    text and panorama branches, dropout state -- and the library calls both issue with the same arguments.  The two schedules
+    themselves (which stream, which order) stay written out in each class."""
+
+    def _stage(self, model: GlocalTextPathNavCMT, batch, n_inputs: int, dropout, drop_seed: int, p_env: float):
+        self.model = model
+        eng = self.eng = model._engine
+        eng.require_gpu()
+        self.L = eng.L
+        if dropout == "config":                # the model config's rates, the reference's policy.train()
+            dropout = config_dropout_rates(model.config) + (float(p_env),)
+        self.dropout, self.drop_seed, self.step_no = dropout, int(drop_seed) & 0xFFFFFFFF, 0
+        B, Lt = self.B, self.Lt = batch["txt_ids"].shape
+        # Panorama batch: B (one panorama per episode) or the sum of trajectory steps; the node features are a CSR gather over all
+        # panorama embeddings either way.
+        Bp, V = self.Bp, self.V = batch["rgb_fts"].shape[:2]
+        G = self.G = batch["gmap_step_ids"].shape[1]
+        dev, H, h = eng.device, eng.cconf.hidden, eng.handle
+        self.inp = {k: batch[src].to(dt).contiguous().to(dev) for k, src, dt in INPUTS[:n_inputs]}
+        self.csr_f, self.csr_b = _node_csr(batch, V, G, dev)
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)   # API tensors are fp32 in both modes
+        self.txt, self.pano, self.pmask, self.gimg = e(B, Lt, H), e(Bp, V, H), e(Bp, V, dt=torch.bool), e(B, G, H)
+        self.d_txt, self.d_gimg, self.d_pano = e(B, Lt, H), e(B, G, H), e(Bp, V, H)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        # separate backward workspaces: the backward passes may run on parallel streams
+        self.st_txt, self.ws_txt = eng.buf(self.L.etp_txt_stash_bytes(h, B, Lt)), eng.buf(self.L.etp_txt_ws_bytes(h, B, Lt))
+        self.st_pano, self.ws_pano = eng.buf(self.L.etp_pano_stash_bytes(h, Bp, V)), eng.buf(self.L.etp_pano_ws_bytes(h, Bp, V))
+        return e                               # the allocator, for the tensors only one of the two steps has
+
+    def _drop_state(self):
+        if self.dropout is None:
+            return None
+        return tuple(self.dropout) + ((self.drop_seed << 32) | (self.step_no & 0xFFFFFFFF),)
+
+    def _refresh_side_weights(self, s2: int):
+        check(self.L.etp_planner_refresh_part(self.eng.handle, 1, s2), "refresh panorama weights")
+        check(self.L.etp_planner_refresh_part(self.eng.handle, 2, s2), "refresh navigation weights")
+
+    def _txt_fwd(self, s: int):
+        i = self.inp
+        check(self.L.etp_txt_fwd(self.eng.handle, ptr(i["txt_ids"]), ptr(i["txt_masks"]), self.B, self.Lt, ptr(self.txt),
+                                 ptr(self.st_txt), s), "txt_fwd")
+
+    def _pano_fwd(self, s2: int):
+        i = self.inp
+        check(self.L.etp_pano_fwd(self.eng.handle, ptr(i["rgb"]), ptr(i["dep"]), ptr(i["loc"]), ptr(i["nav"]), ptr(i["view_lens"]),
+                                  self.Bp, self.V, ptr(self.pano), ptr(self.pmask), ptr(self.st_pano), s2), "pano_fwd")
+
+    def _pano_bwd(self, s2: int):
+        i = self.inp
+        check(self.L.etp_pano_bwd(self.eng.handle, ptr(self.d_pano), ptr(i["rgb"]), ptr(i["dep"]), ptr(i["loc"]), ptr(i["nav"]),
+                                  self.Bp, self.V, None, ptr(self.st_pano), ptr(self.ws_pano), s2), "pano_bwd")
+
+    def _assemble(self, s: int):
+        """node features = gather-mean of the view embeddings (fp32 API tensors)"""
+        pf, xf, wf = self.csr_f
+        check(self.L.etp_gather_sum(_lib.ETP_F32, ptr(self.pano), ptr(pf), ptr(xf), ptr(wf), ptr(self.gimg), self.B * self.G,
+                                    self.eng.cconf.hidden, 0, s), "node assembly")
+
+    def _assemble_bwd(self, s: int):
+        pb, xb, wb = self.csr_b
+        check(self.L.etp_gather_sum(_lib.ETP_F32, ptr(self.d_gimg), ptr(pb), ptr(xb), ptr(wb), ptr(self.d_pano), self.Bp * self.V,
+                                    self.eng.cconf.hidden, 0, s), "node assembly bwd")
+
+
+class PlannerStep(_Staging):
     def __init__(self, model: GlocalTextPathNavCMT, batch: Dict[str, torch.Tensor], overlap: bool = True,
                  dropout=None, drop_seed: int = 0, refresh_weights: bool = True, zero_grads: bool = True,
                  grad_overwrite: Optional[bool] = None, share_side_streams: Optional["PlannerStep"] = None):
         """dropout: None (eval-mode step), "config" (the model config's rates, the reference's policy.train()), or a
         tuple (p_hidden, p_attn, p_head, p_env).  refresh_weights / zero_grads = False when etpnav_amd.optim.FusedAdamW
         closes the step: its kernel already wrote the bf16 weight shadow and zeroed the gradient arena.
-        grad_overwrite: weight-gradient GEMMs store instead of accumulating (etp_planner_set_grad_overwrite) and only the
+        grad_overwrite: weight-gradient GEMMs store instead of accumulating (Engine.scope's grad_overwrite mode) and only the
         vector/table tail of the gradient arena is zeroed per step.  Default: on when this step owns the zeroing (fresh
         gradients every step) and every weight matrix is touched exactly once per step (not the pre-training variant, whose
         language-side x-layer weights this step does not touch)."""
-        self.model = model
         self.refresh_weights, self.zero_grads = refresh_weights, zero_grads
         # frozen sub-models (vlnbert_init.py:51-54 -> vilmodel_cmt.py:422-433,675-682): with fix_lang_embedding the text encoder's
         # output is detached (LanguageEncoder.forward :431-432) -- no text backward runs and no gradient reaches `embeddings.*` /
@@ -79,88 +176,36 @@ class PlannerStep:
         # (frozen) panorama encoder to reach it; only with BOTH flags nothing behind the panorama branch requires a gradient
         # (the features are inputs) and autograd never enters it -- neither does this step.  Gradient slots of frozen parameters
         # in the flat arena are unspecified (their .grad is None, FusedAdamW and the data-parallel buckets leave them out).
-        from .planner import _cfg_get
         self.train_txt = not bool(_cfg_get(model.config, "fix_lang_embedding", False))
         self.train_pano = self.train_txt or not bool(_cfg_get(model.config, "fix_pano_embedding", False))
         if grad_overwrite is None:
             grad_overwrite = bool(zero_grads) and not model._engine.cconf.use_lang2visn and \
                 os.environ.get("ETP_GRAD_OVERWRITE", "1") != "0"
         self.grad_overwrite = bool(grad_overwrite)
-        if dropout == "config":
-            c = model.config
-            dropout = (float(getattr(c, "hidden_dropout_prob", 0.1)), float(getattr(c, "attention_probs_dropout_prob", 0.1)),
-                       float(getattr(c, "pred_head_dropout_prob", 0.1)), float(model.drop_env_prob))
-        self.dropout = dropout
-        self.drop_seed = int(drop_seed) & 0xFFFFFFFF
-        self.step_no = 0
-        self.loss_scale = 1.0 / batch["txt_ids"].shape[0]      # cross_entropy(sum) / batch_size (ss_trainer_ETP.py:892)
-        eng = self.eng = model._engine
-        eng.require_gpu()
-        dev = eng.device
-        self.L = eng.L
-        self.B, self.Lt = batch["txt_ids"].shape
-        self.V = batch["rgb_fts"].shape[1]
-        self.G = batch["gmap_step_ids"].shape[1]
-        B, Lt, V, G, H = self.B, self.Lt, self.V, self.G, eng.cconf.hidden
-        t = eng.tdtype
-        mv = lambda x, dt=None: (x.to(dt) if dt is not None else x).contiguous().to(dev)
-        self.inp = {
-            "txt_ids": mv(batch["txt_ids"], torch.int64), "txt_masks": mv(batch["txt_masks"], torch.bool),
-            "rgb": mv(batch["rgb_fts"], torch.float32), "dep": mv(batch["dep_fts"], torch.float32),
-            "loc": mv(batch["loc_fts"], torch.float32), "nav": mv(batch["nav_types"], torch.int64),
-            "view_lens": mv(batch["view_lens"], torch.int64), "step_ids": mv(batch["gmap_step_ids"], torch.int64),
-            "pos": mv(batch["gmap_pos_fts"], torch.float32), "gmask": mv(batch["gmap_masks"], torch.bool),
-            "visited": mv(batch["gmap_visited_masks"], torch.bool), "dists": mv(batch["gmap_pair_dists"], torch.float32),
-            "labels": mv(batch["labels"], torch.int64),
-        }
-        # Panorama batch: B (one panorama per episode, the fine-tuning rollout step) or sum of trajectory steps (the
-        # pre-training SAP task, pretrain_cmt.py:223-283: one panorama per step of every episode); the node features are a
-        # CSR gather over all panorama embeddings either way.
-        Bp = self.Bp = batch["rgb_fts"].shape[0]
-        if "traj" in batch:
-            from .graph_inputs import pack_traj_csr
-            tr = batch["traj"]
-            (pf, xf, wf), (pb, xb, wb) = pack_traj_csr(tr["traj_vp_lens"], tr["traj_vpids"], tr["traj_cand_vpids"],
-                                                       tr["gmap_vpids"], V, G)
-        else:
-            if Bp != B:
-                raise ValueError("rgb_fts batch differs from txt_ids batch: pass the trajectory lists as batch['traj']")
-            (pf, xf, wf), (pb, xb, wb) = build_node_csr(batch["view_lens"].cpu(), V, G)
-        self.csr_f = tuple(x.to(dev) for x in (pf, xf, wf))
-        self.csr_b = tuple(x.to(dev) for x in (pb, xb, wb))
-        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)   # API tensors are fp32 in both modes
-        self.txt = e(B, Lt, H); self.pano = e(Bp, V, H); self.pmask = e(Bp, V, dt=torch.bool)
-        self.gimg = e(B, G, H); self.gemb = e(B, G, H); self.logits = e(B, G, dt=torch.float32)
-        self.dlogits = e(B, G, dt=torch.float32); self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.d_txt = e(B, Lt, H); self.d_gimg = e(B, G, H); self.d_pano = e(Bp, V, H)
-        h = eng.handle
-        self.st_txt = eng.buf(self.L.etp_txt_stash_bytes(h, B, Lt))
-        self.st_pano = eng.buf(self.L.etp_pano_stash_bytes(h, Bp, V))
+        e = self._stage(model, batch, len(INPUTS), dropout, drop_seed, model.drop_env_prob)
+        self.loss_scale = 1.0 / self.B                         # cross_entropy(sum) / batch_size (ss_trainer_ETP.py:892)
+        eng, h, (B, Lt, G) = self.eng, self.eng.handle, (self.B, self.Lt, self.G)
+        self.gemb, self.logits, self.dlogits = e(B, G, eng.cconf.hidden), e(B, G), e(B, G)
         self.st_nav = eng.buf(self.L.etp_nav_stash_bytes(h, B, Lt, G))
-        # separate backward workspaces: the three backward passes may run on parallel streams
-        self.ws_txt = eng.buf(self.L.etp_txt_ws_bytes(h, B, Lt))
-        self.ws_pano = eng.buf(self.L.etp_pano_ws_bytes(h, Bp, V))
         self.ws_nav = eng.buf(self.L.etp_nav_ws_bytes(h, B, Lt, G))
-        # side streams: `aux` carries the weight-gradient GEMMs, `s2` the panorama branch (independent of the text branch)
+        # side streams: `aux` carries the weight-gradient GEMMs, `s2` the panorama branch (independent of the text branch), `aux2`
+        # the d txt_embeds chain of the navigation backward
         self.overlap = overlap
-        self.aux = self.s2 = None
+        self.aux = self.s2 = self.aux2 = None
         # leaf work (weight gradients; the panorama branch) runs at the lowest stream priority: whenever its workgroups and the
         # dependent chain's wait for the same CUs, the chain's are dispatched first (ETP_STREAM_PRIO=0: all default)
         low = -1 if os.environ.get("ETP_STREAM_PRIO", "1") != "0" else 0
         self._own_aux = share_side_streams is None
         if not self._own_aux:                  # MicroBatchedStep: one weight-gradient / d_txt stream for all micro-batches
-            self.aux = share_side_streams.aux
+            self.aux, self.aux2 = share_side_streams.aux, share_side_streams.aux2
         elif overlap in (True, "aux", "both"):
-            self.aux = _side_stream(self.L, low)
+            self.aux = _new_stream(self.L, low)
         if overlap in (True, "s2", "both"):
-            self.s2 = _side_stream(self.L, low)
-        self.aux2 = None
-        if not self._own_aux:
-            self.aux2 = share_side_streams.aux2
-        elif self.aux is not None and os.environ.get("ETP_DTXT_STREAM", "1") != "0":
-            a2 = ctypes.c_void_p()
-            check(self.L.etp_stream_create(ctypes.byref(a2)), "stream_create")
-            self.aux2 = a2.value
+            self.s2 = _new_stream(self.L, low)
+        if self._own_aux and self.aux is not None and os.environ.get("ETP_DTXT_STREAM", "1") != "0":
+            self.aux2 = _new_stream(self.L)
+        # lazy joins: navigation / panorama weight gradients keep running on the aux stream while the text backward starts; the text
+        # backward's own join (or the explicit one in enqueue_bwd_main) completes them
         self._lazy = 1 if self.aux is not None else 0
         # schedule switches are read ONCE, here (no environment lookups on the per-step path)
         self._txt_cast_split = os.environ.get("ETP_TXT_CAST_SPLIT", "1") != "0"
@@ -168,22 +213,20 @@ class PlannerStep:
         # node assembly (gather-mean of the view embeddings) rides behind pano_fwd on the panorama stream, off the chain (round 6: -0.35 %,
         # 4.045 against 4.059 ms, three pairs, profiles/r06_ab_runs.json r6c9); ETP_ASSEMBLE_ON_S2=0 puts it back behind the join
         self._assemble_on_s2 = os.environ.get("ETP_ASSEMBLE_ON_S2", "1") != "0"
-        self._install_streams()
+        with eng.scope(aux=self.aux, aux2=self.aux2, lazy=self._lazy):
+            pass                               # the bridges' join_aux sees this step's streams from now on
         self._pano_pending = False
         self.graph = None
         self.graphs = []
         self.stream = None
 
-    def _install_streams(self):
+    def _scope(self, lazy: Optional[int] = None):
         """The planner handle is shared by every step object of a model (PretrainDriver alternates MlmStep and several cached
-        PlannerSteps): its side streams and lazy-join level are (re)installed at every enqueue, so a step never runs on another
-        step's streams or silently loses its overlap schedule.  navigation / panorama weight gradients keep running on the aux
-        stream while the text backward starts; the text backward's own join (or the explicit one in enqueue_main) completes
-        them."""
-        h = self.eng.handle
-        check(self.L.etp_planner_set_aux_stream(h, self.aux), "set_aux_stream")
-        check(self.L.etp_planner_set_aux2_stream(h, self.aux2), "set_aux2_stream")
-        check(self.L.etp_planner_set_lazy_join(h, self._lazy), "set_lazy_join")
+        PlannerSteps): side streams, lazy-join level, dropout state and overwrite mode are (re)installed at every enqueue, so a
+        step never runs on another step's streams or silently loses its overlap schedule.  lazy = 2: a text-backward range above
+        layer 0 that does not join (the next range continues the chain)."""
+        return self.eng.scope(aux=self.aux, aux2=self.aux2, lazy=self._lazy if lazy is None else lazy, drop=self._drop_state(),
+                              grad_overwrite=self.grad_overwrite)
 
     def shape_key(self):
         return (self.B, self.Lt, self.Bp, self.V, self.G)
@@ -202,34 +245,16 @@ class PlannerStep:
         if self.graphs:
             # the CSR index tensors below are re-allocated: kernel nodes of an existing graph would keep the old pointers
             raise RuntimeError("load_batch() on a step with captured / recorded graphs: close() the graphs (or build a new step) first")
-        names = {"txt_ids": "txt_ids", "txt_masks": "txt_masks", "rgb": "rgb_fts", "dep": "dep_fts", "loc": "loc_fts", "nav": "nav_types",
-                 "view_lens": "view_lens", "step_ids": "gmap_step_ids", "pos": "gmap_pos_fts", "gmask": "gmap_masks",
-                 "visited": "gmap_visited_masks", "dists": "gmap_pair_dists", "labels": "labels"}
-        for k, src in names.items():
-            t = self.inp[k]
-            t.copy_(batch[src].to(t.dtype), non_blocking=True)
-        dev = self.eng.device
-        if "traj" in batch:
-            from .graph_inputs import pack_traj_csr
-            tr = batch["traj"]
-            f, b = pack_traj_csr(tr["traj_vp_lens"], tr["traj_vpids"], tr["traj_cand_vpids"], tr["gmap_vpids"], self.V, self.G)
-        else:
-            f, b = build_node_csr(batch["view_lens"].cpu(), self.V, self.G)
-        self.csr_f = tuple(x.to(dev) for x in f)
-        self.csr_b = tuple(x.to(dev) for x in b)
+        for k, src, dt in INPUTS:
+            self.inp[k].copy_(batch[src].to(dt), non_blocking=True)
+        self.csr_f, self.csr_b = _node_csr(batch, self.V, self.G, self.eng.device)
 
     # ------------------------------------------------------------------------------------------
     def _enqueue_pano_bwd(self, s: int):
         if not self.train_pano:
             return
-        L, h, i = self.L, self.eng.handle, self.inp
-        s2 = self.s2 if self.s2 is not None else s
-        self._install_streams()
-        self.eng.set_dropout(self._drop_state())
-        check(L.etp_planner_set_grad_overwrite(h, int(self.grad_overwrite)), "set_grad_overwrite")
-        check(L.etp_pano_bwd(h, ptr(self.d_pano), ptr(i["rgb"]), ptr(i["dep"]), ptr(i["loc"]), ptr(i["nav"]), self.Bp, self.V, None,
-                             ptr(self.st_pano), ptr(self.ws_pano), s2), "pano_bwd")
-        check(L.etp_planner_set_grad_overwrite(h, 0), "set_grad_overwrite")
+        with self._scope():
+            self._pano_bwd(self.s2 if self.s2 is not None else s)
         self._pano_pending = True
 
     def enqueue_main(self, s: int, backward: bool = True, join_pano: bool = True, defer_pano: bool = False):
@@ -244,93 +269,77 @@ class PlannerStep:
         """weight refresh, gradient zeroing, forward_txt || forward_panorama, node assembly, forward_navigation, loss"""
         s2 = self.s2 if self.s2 is not None else s
         L, eng, h, i = self.L, self.eng, self.eng.handle, self.inp
-        B, Lt, V, G, H = self.B, self.Lt, self.V, self.G, eng.cconf.hidden
-        dt = _lib.ETP_F32          # node assembly works on the fp32 API tensors
+        B, Lt, G = self.B, self.Lt, self.G
         self.step_no += 1
-        self._install_streams()
-        eng.set_dropout(self._drop_state())
-        check(L.etp_planner_set_grad_overwrite(h, int(self.grad_overwrite)), "set_grad_overwrite")
-        L.etp_stamp_mark(s, 1)                 # measurement aid: a no-op unless a stamp sink is installed (tools/chain_waits.py)
-        # weight-shadow refresh and gradient zeroing ride on the stream that first needs them: the text cast on the main
-        # stream, the panorama/navigation casts and the (bandwidth-bound) gradient memset on the panorama stream, whose
-        # join below precedes forward_navigation and every backward kernel
-        if self.refresh_weights:
-            # only layer 0's cast stays in front of the first text GEMM; layers 1.. are cast on the panorama stream and
-            # etp_txt_fwd waits for them after its layer 0 (ETP_TXT_CAST_SPLIT=0: the whole text cast on the main stream)
-            if self.s2 is not None and self._txt_cast_split:
-                check(L.etp_planner_refresh_text_split(h, s, s2), "refresh text weights")
-            else:
-                check(L.etp_planner_refresh_part(h, 0, s), "refresh text weights")
-        check(L.etp_stream_after(s, s2), "fork")
-        if self.refresh_weights:
-            check(L.etp_planner_refresh_part(h, 1, s2), "refresh panorama weights")
-            check(L.etp_planner_refresh_part(h, 2, s2), "refresh navigation weights")
-        if backward and self.zero_grads:
-            # overwrite mode: the matrix region [0, n_matrix) is fully rewritten by this step's weight-gradient stores
-            # (round 6: navigation cast + this memset BEHIND the panorama branch instead of in front of it: no gain, r06_ab_runs.json r6c11;
-            # the memset beside forward_navigation, the backward waiting for it: +0.7 %, 3.952 against 3.924 ms, four pairs, r6c16)
-            lo = eng.n_matrix if self.grad_overwrite else 0
-            check(L.etp_memset_async(eng.grads.data_ptr() + lo * 4, 0, (eng.grads.numel() - lo) * 4, s2), "memset grads")
-        if after_prologue is not None:         # MicroBatchedStep: the other micro-batches' streams are ordered after the casts / memset
-            after_prologue(s, s2)
-        check(L.etp_txt_fwd(h, ptr(i["txt_ids"]), ptr(i["txt_masks"]), B, Lt, ptr(self.txt), ptr(self.st_txt), s), "txt_fwd")
-        check(L.etp_pano_fwd(h, ptr(i["rgb"]), ptr(i["dep"]), ptr(i["loc"]), ptr(i["nav"]), ptr(i["view_lens"]), self.Bp, V,
-                             ptr(self.pano), ptr(self.pmask), ptr(self.st_pano), s2), "pano_fwd")
-        pf, xf, wf = self.csr_f
-        if self._assemble_on_s2 and s2 != s:   # the gather-mean of the view embeddings depends on the panorama branch only: behind it, off the chain
-            check(L.etp_gather_sum(dt, ptr(self.pano), ptr(pf), ptr(xf), ptr(wf), ptr(self.gimg), B * G, H, 0, s2), "node assembly")
-        check(L.etp_stream_after(s2, s), "join")
-        L.etp_stamp_mark(s, 2)
-        if not (self._assemble_on_s2 and s2 != s):
-            check(L.etp_gather_sum(dt, ptr(self.pano), ptr(pf), ptr(xf), ptr(wf), ptr(self.gimg), B * G, H, 0, s), "node assembly")
-        check(L.etp_nav_fwd(h, ptr(self.txt), ptr(i["txt_masks"]), ptr(i["step_ids"]), ptr(self.gimg), ptr(i["pos"]),
-                            ptr(i["gmask"]), ptr(i["visited"]), ptr(i["dists"]), B, Lt, G, ptr(self.gemb), ptr(self.logits),
-                            ptr(self.st_nav), s), "nav_fwd")
-        check(L.etp_sap_ce(ptr(self.logits), ptr(i["labels"]), ptr(self.loss), ptr(self.dlogits) if backward else None, B, G,
-                           self.loss_scale, -100, s), "sap_ce")
-        L.etp_stamp_mark(s, 3)
-        check(L.etp_planner_set_grad_overwrite(h, 0), "set_grad_overwrite")     # the mode never leaks to other users of the planner
+        with self._scope():
+            L.etp_stamp_mark(s, 1)             # measurement aid: a no-op unless a stamp sink is installed (tools/chain_waits.py)
+            # weight-shadow refresh and gradient zeroing ride on the stream that first needs them: the text cast on the main
+            # stream, the panorama/navigation casts and the (bandwidth-bound) gradient memset on the panorama stream, whose
+            # join below precedes forward_navigation and every backward kernel
+            if self.refresh_weights:
+                # only layer 0's cast stays in front of the first text GEMM; layers 1.. are cast on the panorama stream and
+                # etp_txt_fwd waits for them after its layer 0 (ETP_TXT_CAST_SPLIT=0: the whole text cast on the main stream)
+                if self.s2 is not None and self._txt_cast_split:
+                    check(L.etp_planner_refresh_text_split(h, s, s2), "refresh text weights")
+                else:
+                    check(L.etp_planner_refresh_part(h, 0, s), "refresh text weights")
+            check(L.etp_stream_after(s, s2), "fork")
+            if self.refresh_weights:
+                self._refresh_side_weights(s2)
+            if backward and self.zero_grads:
+                # overwrite mode: the matrix region [0, n_matrix) is fully rewritten by this step's weight-gradient stores
+                # (round 6: navigation cast + this memset BEHIND the panorama branch instead of in front of it: no gain, r06_ab_runs.json r6c11;
+                # the memset beside forward_navigation, the backward waiting for it: +0.7 %, 3.952 against 3.924 ms, four pairs, r6c16)
+                lo = eng.n_matrix if self.grad_overwrite else 0
+                check(L.etp_memset_async(eng.grads.data_ptr() + lo * 4, 0, (eng.grads.numel() - lo) * 4, s2), "memset grads")
+            if after_prologue is not None:     # MicroBatchedStep: the other micro-batches' streams are ordered after the casts / memset
+                after_prologue(s, s2)
+            self._txt_fwd(s)
+            self._pano_fwd(s2)
+            on_s2 = self._assemble_on_s2 and s2 != s
+            if on_s2:                          # the gather-mean of the view embeddings depends on the panorama branch only: behind it, off the chain
+                self._assemble(s2)
+            check(L.etp_stream_after(s2, s), "join")
+            L.etp_stamp_mark(s, 2)
+            if not on_s2:
+                self._assemble(s)
+            check(L.etp_nav_fwd(h, ptr(self.txt), ptr(i["txt_masks"]), ptr(i["step_ids"]), ptr(self.gimg), ptr(i["pos"]),
+                                ptr(i["gmask"]), ptr(i["visited"]), ptr(i["dists"]), B, Lt, G, ptr(self.gemb), ptr(self.logits),
+                                ptr(self.st_nav), s), "nav_fwd")
+            check(L.etp_sap_ce(ptr(self.logits), ptr(i["labels"]), ptr(self.loss), ptr(self.dlogits) if backward else None, B, G,
+                               self.loss_scale, -100, s), "sap_ce")
+            L.etp_stamp_mark(s, 3)
 
     def enqueue_bwd_main(self, s: int, join_pano: bool = True, defer_pano: bool = False):
         """navigation backward, node assembly backward, panorama backward (on the panorama stream)"""
         s2 = self.s2 if self.s2 is not None else s
-        L, eng, h, i = self.L, self.eng, self.eng.handle, self.inp
-        B, Lt, V, G, H = self.B, self.Lt, self.V, self.G, eng.cconf.hidden
-        dt = _lib.ETP_F32
-        self._install_streams()
-        eng.set_dropout(self._drop_state())
-        check(L.etp_planner_set_grad_overwrite(h, int(self.grad_overwrite)), "set_grad_overwrite")
-        check(L.etp_nav_bwd(h, None, ptr(self.dlogits), ptr(self.txt), ptr(i["txt_masks"]), ptr(i["step_ids"]),
-                            ptr(i["pos"]), ptr(i["gmask"]), ptr(i["visited"]), ptr(i["dists"]), B, Lt, G, ptr(self.d_txt),
-                            ptr(self.d_gimg), ptr(self.st_nav), ptr(self.ws_nav), s), "nav_bwd")
-        pb, xb, wb = self.csr_b
-        L.etp_stamp_mark(s, 4)
-        if not self.train_pano:    # frozen panorama embedding: the backward stops at the node features (d_gimg)
+        L, h, i = self.L, self.eng.handle, self.inp
+        with self._scope():
+            check(L.etp_nav_bwd(h, None, ptr(self.dlogits), ptr(self.txt), ptr(i["txt_masks"]), ptr(i["step_ids"]),
+                                ptr(i["pos"]), ptr(i["gmask"]), ptr(i["visited"]), ptr(i["dists"]), self.B, self.Lt, self.G,
+                                ptr(self.d_txt), ptr(self.d_gimg), ptr(self.st_nav), ptr(self.ws_nav), s), "nav_bwd")
+            L.etp_stamp_mark(s, 4)
+            if not self.train_pano:            # frozen panorama embedding: the backward stops at the node features (d_gimg)
+                if join_pano:
+                    check(L.etp_planner_join_aux(h, s), "join aux")
+                return
+            # (round 6: this gather on the panorama stream behind the fork instead -- it feeds the panorama backward only -- measured neutral,
+            # 3.971 against 3.969 ms over four pairs, r06_ab_runs.json r6c14: the text backward waits for d txt_embeds meanwhile anyway)
+            self._assemble_bwd(s)
+            L.etp_stamp_mark(s, 5)
+            check(L.etp_stream_after(s, s2), "fork")
+            if defer_pano:                     # the caller enqueues the panorama backward later (run_eager: after the first text layers);
+                return                         # its stream is ordered after d_pano's producer already now
+            self._pano_bwd(s2)
             if join_pano:
-                check(L.etp_planner_join_aux(h, s), "join aux")
-            check(L.etp_planner_set_grad_overwrite(h, 0), "set_grad_overwrite")
-            return
-        # (round 6: this gather on the panorama stream behind the fork instead -- it feeds the panorama backward only -- measured neutral,
-        # 3.971 against 3.969 ms over four pairs, r06_ab_runs.json r6c14: the text backward waits for d txt_embeds meanwhile anyway)
-        check(L.etp_gather_sum(dt, ptr(self.d_gimg), ptr(pb), ptr(xb), ptr(wb), ptr(self.d_pano), self.Bp * V, H, 0, s),
-              "node assembly bwd")
-        L.etp_stamp_mark(s, 5)
-        if defer_pano:             # the caller enqueues the panorama backward later (run_eager: after the first text layers);
-            check(L.etp_stream_after(s, s2), "fork")             # its stream is ordered after d_pano's producer already now
-            check(L.etp_planner_set_grad_overwrite(h, 0), "set_grad_overwrite")
-            return
-        check(L.etp_stream_after(s, s2), "fork")
-        check(L.etp_pano_bwd(h, ptr(self.d_pano), ptr(i["rgb"]), ptr(i["dep"]), ptr(i["loc"]), ptr(i["nav"]), self.Bp, V, None,
-                             ptr(self.st_pano), ptr(self.ws_pano), s2), "pano_bwd")
-        if join_pano:
-            check(L.etp_stream_after(s2, s), "join")
-            check(L.etp_planner_join_aux(h, s), "join aux")      # callers of this mode read the non-text gradients next
-        else:
-            self._pano_pending = True
-        check(L.etp_planner_set_grad_overwrite(h, 0), "set_grad_overwrite")     # the mode never leaks to other users of the planner
+                check(L.etp_stream_after(s2, s), "join")
+                check(L.etp_planner_join_aux(h, s), "join aux")      # callers of this mode read the non-text gradients next
+            else:
+                self._pano_pending = True
 
-    def enqueue_txt_bwd(self, s: int, layer_lo: int = 0, layer_hi: Optional[int] = None):
-        """Text-encoder backward (optionally only layers [layer_lo, layer_hi), descending calls share the running gradient)."""
+    def enqueue_txt_bwd(self, s: int, layer_lo: int = 0, layer_hi: Optional[int] = None, lazy: Optional[int] = None):
+        """Text-encoder backward (optionally only layers [layer_lo, layer_hi), descending calls share the running gradient; `lazy`:
+        the lazy-join level of this range, see _scope)."""
         L, eng, i = self.L, self.eng, self.inp
         if layer_hi is None:
             layer_hi = eng.cconf.n_l
@@ -338,13 +347,10 @@ class PlannerStep:
             if layer_lo == 0:
                 self._join_side(s)
             return
-        self._install_streams()
-        eng.set_dropout(self._drop_state())
-        check(L.etp_planner_set_grad_overwrite(eng.handle, int(self.grad_overwrite)), "set_grad_overwrite")
-        L.etp_stamp_mark(s, 6)
-        check(L.etp_txt_bwd_range(eng.handle, ptr(self.d_txt), ptr(i["txt_ids"]), ptr(i["txt_masks"]), self.B, self.Lt,
-                                  ptr(self.st_txt), ptr(self.ws_txt), layer_lo, layer_hi, s), "txt_bwd")
-        check(L.etp_planner_set_grad_overwrite(eng.handle, 0), "set_grad_overwrite")
+        with self._scope(lazy):
+            L.etp_stamp_mark(s, 6)
+            check(L.etp_txt_bwd_range(eng.handle, ptr(self.d_txt), ptr(i["txt_ids"]), ptr(i["txt_masks"]), self.B, self.Lt,
+                                      ptr(self.st_txt), ptr(self.ws_txt), layer_lo, layer_hi, s), "txt_bwd")
         if layer_lo > 0:
             return
         if self._pano_pending:
@@ -361,11 +367,6 @@ class PlannerStep:
             self._pano_pending = False
         self.L.etp_stamp_mark(s, 7)
 
-    def _drop_state(self):
-        if self.dropout is None:
-            return None
-        return tuple(self.dropout) + ((self.drop_seed << 32) | (self.step_no & 0xFFFFFFFF),)
-
     def run_eager(self, stream: Optional[int] = None, backward: bool = True):
         """Enqueue one step on `stream` (default: torch's current stream).  With dropout on, every call draws fresh
         masks (the step counter is part of the seed); a captured graph replays the masks it was captured with.
@@ -381,12 +382,8 @@ class PlannerStep:
         head = max(0, min(3, n_l - 1)) if self._chain_first else 0
         self.enqueue_main(s, True, join_pano=False, defer_pano=head > 0)   # panorama backward overlaps the text backward
         if head > 0:
-            lazy = self.aux is not None
-            if lazy:      # the top layers' weight gradients keep running while the chain continues (no join between the ranges)
-                self._lazy = 2
-            self.enqueue_txt_bwd(s, n_l - head, n_l)
-            if lazy:
-                self._lazy = 1
+            # the top layers' weight gradients keep running while the chain continues (no join between the ranges)
+            self.enqueue_txt_bwd(s, n_l - head, n_l, lazy=2 if self._lazy else 0)
             self._enqueue_pano_bwd(s)
             self.enqueue_txt_bwd(s, 0, n_l - head)
         else:
@@ -420,82 +417,66 @@ class PlannerStep:
             bucket_ready(0, side)
             self._join_side(s)
             return
-        self._lazy = 2                                       # no join between the layer groups; the last group (layer 0) joins
-        try:
-            for k, (lo, hi) in enumerate(groups):
-                self.enqueue_txt_bwd(s, lo, hi)
-                if k == 0:
-                    bucket_ready(0, side)                    # issued after the first group: the panorama branch gets a head start
-                bucket_ready(1 + k, (self.aux,))
-        finally:
-            self._lazy = 1
+        for k, (lo, hi) in enumerate(groups):
+            self.enqueue_txt_bwd(s, lo, hi, lazy=2)          # no join between the layer groups; the last group (layer 0) joins
+            if k == 0:
+                bucket_ready(0, side)                        # issued after the first group: the panorama branch gets a head start
+            bucket_ready(1 + k, (self.aux,))
 
     # ------------------------------------------------------------------------------------------
-    def _capture_one(self, fn):
-        check(self.L.etp_graph_begin(self.stream), "graph_begin")
-        try:
-            fn(self.stream)
-        finally:
-            g = ctypes.c_void_p()
-            rc = self.L.etp_graph_end(self.stream, ctypes.byref(g))
-        check(rc, "graph_end")
-        return g.value
+    def _build_graphs(self, begin, end, abort, backward: bool, split_text_bwd: bool):
+        """capture() and record(): warm up eagerly (kernel attributes, lazy allocations), then build the step's graph(s) on a
+        private stream between begin() and end() -> graph handle; abort() when the step raises in between.  With split_text_bwd
+        the text-encoder backward is a second graph so that a gradient all-reduce of everything else can be issued between the
+        two (data-parallel overlap)."""
+        torch.cuda.synchronize()
+        self.run_eager(backward=backward)
+        torch.cuda.synchronize()
+        self.stream = _new_stream(self.L)
+        self.graphs, self.graph_stats = [], []
+        if backward and split_text_bwd:
+            fns = (lambda st: self.enqueue_main(st, True), self.enqueue_txt_bwd)
+        else:
+            fns = (lambda st: self.run_eager(stream=st, backward=backward),)
+        for fn in fns:
+            check(begin(), "graph begin")
+            try:
+                fn(self.stream)
+            except Exception:
+                abort()
+                raise
+            self.graphs.append(end())
+        self.graph = self.graphs[0]
+        return self
 
     def capture(self, backward: bool = True, split_text_bwd: bool = False):
-        """Warm up eagerly (sets kernel attributes), then capture the step into hipGraph(s) on a private stream.
-        With split_text_bwd the text-encoder backward is a second graph so that a gradient all-reduce of everything
-        else can be issued between the two (data-parallel overlap)."""
+        """Capture the step into hipGraph(s) by stream capture (see _build_graphs)."""
         if self.aux is not None and self.s2 is not None and not os.environ.get("ETP_GRAPH_FORCE"):
             raise _lib.EtpError("hipGraph capture with two side streams crashes hipStreamEndCapture on ROCm 7.2; "
                                 "build the PlannerStep with overlap='s2', 'aux' or False for graph replay "
                                 "(measured on MI355X: eager two-stream issue is the fastest mode anyway)")
-        torch.cuda.synchronize()
-        self.run_eager(backward=backward)
-        torch.cuda.synchronize()
-        s = ctypes.c_void_p()
-        check(self.L.etp_stream_create(ctypes.byref(s)), "stream_create")
-        self.stream = s.value
-        self.graphs = []
-        if backward and split_text_bwd:
-            self.graphs.append(self._capture_one(lambda st: self.enqueue_main(st, True)))
-            self.graphs.append(self._capture_one(self.enqueue_txt_bwd))
-        else:
-            self.graphs.append(self._capture_one(lambda st: self.run_eager(stream=st, backward=backward)))
-        self.graph = self.graphs[0]
-        return self
+
+        def end(checked=True):
+            g = ctypes.c_void_p()
+            rc = self.L.etp_graph_end(self.stream, ctypes.byref(g))
+            if checked:
+                check(rc, "graph_end")
+            return g.value
+
+        return self._build_graphs(lambda: self.L.etp_graph_begin(self.stream), end, lambda: end(False), backward, split_text_bwd)
 
     def record(self, backward: bool = True, split_text_bwd: bool = False):
         """Build the step's hipGraph EXPLICITLY (etp_rec_begin / etp_rec_end: one kernel node per launch, dependencies from
         the per-stream order and the fork/join events) instead of by stream capture -- this keeps the full three-stream
         schedule (capture() cannot: hipStreamEndCapture crashes with two side streams on ROCm 7.2) while the host issues a
         single hipGraphLaunch per step.  Like capture(), a recorded graph replays the dropout masks it was built with."""
-        torch.cuda.synchronize()
-        self.run_eager(backward=backward)          # warm-up: kernel attributes, lazy allocations
-        torch.cuda.synchronize()
-        s = ctypes.c_void_p()
-        check(self.L.etp_stream_create(ctypes.byref(s)), "stream_create")
-        self.stream = s.value
-        self.graphs, self.graph_stats = [], []
-
-        def rec(fn):
-            check(self.L.etp_rec_begin(), "rec_begin")
-            try:
-                fn(self.stream)
-            except Exception:
-                self.L.etp_rec_abort()
-                raise
+        def end():
             g, nk, ne = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
             check(self.L.etp_rec_end(ctypes.byref(g), ctypes.byref(nk), ctypes.byref(ne)), "rec_end")
             self.graph_stats.append((int(nk.value), int(ne.value)))
             return g.value
 
-        if backward and split_text_bwd:
-            self.graphs.append(rec(lambda st: self.enqueue_main(st, True)))
-            self.graphs.append(rec(self.enqueue_txt_bwd))
-        else:
-            self.graphs.append(rec(lambda st: self.run_eager(stream=st, backward=backward)))
-        self.graph = self.graphs[0]
-        return self
+        return self._build_graphs(self.L.etp_rec_begin, end, self.L.etp_rec_abort, backward, split_text_bwd)
 
     def replay(self, part: Optional[int] = None, stream: Optional[int] = None):
         """Launch the captured graph(s) on `stream` (default: torch's current stream, so torch ops order after it)."""
@@ -520,14 +501,12 @@ class PlannerStep:
         for g in getattr(self, "graphs", []) or []:
             self.L.etp_graph_destroy(g)
         self.graphs, self.graph = [], None
-        if self.stream is not None:
-            self.L.etp_stream_destroy(self.stream); self.stream = None
+        _destroy_streams(self.L, self.stream)
+        self.stream = None
         self.L.etp_planner_set_lazy_join(self.eng.handle, 0)
         self.L.etp_planner_set_aux_stream(self.eng.handle, None)
         self.L.etp_planner_set_aux2_stream(self.eng.handle, None)
-        for st in ((self.aux, self.s2, getattr(self, "aux2", None)) if self._own_aux else (self.s2,)):
-            if st is not None:
-                self.L.etp_stream_destroy(st)
+        _destroy_streams(self.L, *((self.aux, self.s2, self.aux2) if self._own_aux else (self.s2,)))
         self.aux = self.s2 = self.aux2 = None
 
 
@@ -566,17 +545,11 @@ class MicroBatchedStep:
                             share_side_streams=self.parts[0] if k > 0 else None)
             p.loss_scale = 1.0 / B
             self.parts.append(p)
-        h = self.eng.handle
         # ONE weight-gradient stream and ONE d_txt stream for all micro-batches: in-order issue is what lets the later
         # micro-batches accumulate onto the first one's stores without atomics
-        check(self.L.etp_planner_set_aux_stream(h, self.parts[0].aux), "set_aux_stream")
-        check(self.L.etp_planner_set_aux2_stream(h, self.parts[0].aux2), "set_aux2_stream")
-        check(self.L.etp_planner_set_lazy_join(h, 1), "set_lazy_join")
-        self.mains = [None]
-        for _ in range(1, n_micro):
-            m = ctypes.c_void_p()
-            check(self.L.etp_stream_create(ctypes.byref(m)), "stream_create")
-            self.mains.append(m.value)
+        with self.eng.scope(aux=self.parts[0].aux, aux2=self.parts[0].aux2, lazy=1):
+            pass
+        self.mains = [None] + [_new_stream(self.L) for _ in range(1, n_micro)]
 
     @property
     def loss(self):
@@ -611,6 +584,5 @@ class MicroBatchedStep:
         torch.cuda.synchronize()
         for p in reversed(self.parts):
             p.close()
-        for m in self.mains[1:]:
-            self.L.etp_stream_destroy(m)
+        _destroy_streams(self.L, *self.mains[1:])
         self.mains = [None]

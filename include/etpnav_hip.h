@@ -462,12 +462,19 @@ int etp_planner_bind(etp_planner* p, float* params, void* shadow, float* grads);
  * chain (works eagerly and under hipGraph capture: the fork/join become graph edges).  NULL = single stream. */
 int etp_planner_set_aux_stream(etp_planner* p, etp_stream_t aux);
 /* Optional third stream for etp_nav_bwd: the d(txt_embeds) contributions of the text K/V projections (vilmodel_cmt.py:326-328,
- * M = B*L rows) accumulate on `aux2` beside the node chain and are joined back before the call returns.  NULL = main stream. */
+ * M = B*L rows) accumulate on `aux2` beside the node chain.  NULL = main stream.  With lazy joins off (below) they are joined
+ * back before the call returns.  With lazy >= 1, etp_nav_bwd returns with d_txt_embeds complete ONLY on `aux2`: it becomes
+ * ordered into `stream` by the next etp_txt_bwd / etp_txt_bwd_range or etp_planner_join_aux ON THE SAME STREAM (the call
+ * remembers which stream is owed the wait).  A caller that reads d_txt_embeds otherwise -- on another stream, with torch, on
+ * the host -- must call etp_planner_join_aux(p, stream) with etp_nav_bwd's stream first. */
 int etp_planner_set_aux2_stream(etp_planner* p, etp_stream_t aux2);
 /* With an aux stream: lazy = 1 lets etp_nav_bwd* / etp_pano_bwd return WITHOUT joining their weight-gradient GEMMs back
  * (nothing downstream of them reads weight gradients), so the text backward does not wait for the navigation weight
  * gradients; the gradients are complete in `stream` order only after a later joining call: etp_txt_bwd / etp_txt_bwd_range
  * / etp_nav_kv_bwd (always join) or etp_planner_join_aux.  Default 0: every backward entry point joins before it returns.
+ * Not only weight gradients are deferred: with an aux2 stream, lazy >= 1 also defers the join of etp_nav_bwd's d_txt_embeds
+ * (see etp_planner_set_aux2_stream: in flight on `aux2` when the call returns, waited for by etp_txt_bwd(_range) and
+ * etp_planner_join_aux on the same stream only).
  * lazy = 2: additionally etp_txt_bwd_range calls that stop above layer 0 do not join (the next range continues the chain). */
 int etp_planner_set_lazy_join(etp_planner* p, int lazy);
 /* on = 1: weight-gradient products STORE into the matrix region [0, etp_planner_matrix_elems) of the gradient arena instead of
