@@ -774,7 +774,11 @@ def vp_feature_variable(obs: dict, device) -> dict:
     """Drop-in for RLTrainer._vp_feature_variable (ss_trainer_ETP.py:308-342) on the device: three gathers
     (etp_vp_gather) instead of per-episode torch.cat / pad loops.  `obs` keys as in the reference: cand_img_idxes,
     cand_rgb, cand_depth, cand_angle_fts (lists of per-episode tensors), pano_rgb [B,12,F], pano_depth [B,12,Fd],
-    pano_angle_fts [12,4].  (Forward only: these are detached perception features in the reference as well.)"""
+    pano_angle_fts [12,4].  (Forward only: these are detached perception features in the reference as well.)
+    An `obs` from ETP.forward(mode='waypoint') with fuse_pano_inputs carries the five tensors already (waypoint.panorama_inputs built
+    them in one launch, csrc/pano_inputs.hip): they are handed on as they are."""
+    if "pano_inputs" in obs:
+        return {k: obs["pano_inputs"][k] for k in ("rgb_fts", "dep_fts", "loc_fts", "nav_types", "view_lens")}
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.EtpError("etp_vp_gather needs an MI355X (cuda/hip device); no CPU fallback exists")

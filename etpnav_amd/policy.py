@@ -32,6 +32,12 @@ class ETP(nn.Module):
         self.space_pool_depth = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), nn.Flatten(start_dim=2))   # :125
         self.space_pool_rgb = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), nn.Flatten(start_dim=2))     # :139
         self.pano_img_idxes, self.pano_angle_fts = pano_constants()                                    # :141-143
+        # mode='waypoint' with fuse_pano_inputs: the planner's panorama inputs (rgb_fts .. view_lens) come out of one launch
+        # (waypoint.panorama_inputs) under 'pano_inputs', and cand_rgb / cand_depth / pano_rgb / pano_depth are not built;
+        # graph_inputs.vp_feature_variable hands them on.  pano_inputs_capacity: None = the reference's padded length, or a fixed
+        # number of view rows (16 suffices for five candidates).  Off: the reference's ten keys, as before.
+        self.fuse_pano_inputs = False
+        self.pano_inputs_capacity = None
 
     def forward(self, mode=None, txt_ids=None, txt_masks=None, txt_embeds=None, waypoint_predictor=None,
                 observations=None, in_train=True, rgb_fts=None, dep_fts=None, loc_fts=None, nav_types=None,

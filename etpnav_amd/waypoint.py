@@ -7,6 +7,9 @@ csrc/waypoint.hip.
     BinaryDistPredictorTRM                            nn.Module with the reference's state-dict names; forward -> logits [B,120,12];
                                                       candidates(logits, in_train, generator) -> CandidateTable
     waypoint_mode(net, predictor, observations, in_train)   the body of ETP.forward(mode='waypoint')
+    panorama_inputs(rgb_embedding, depth_embedding, cand, in_train, V)   etp_pano_inputs: the candidate table and the two embeddings ->
+                                                      the panorama encoder's inputs in one launch (net.fuse_pano_inputs routes
+                                                      waypoint_mode through it)
 
 The predictor is frozen and runs in eval() (ss_trainer_ETP.py:201-202): forward only, parameters do not require gradients.
 There is no CPU fallback: without the built library, or without a GPU, the compute paths raise.
@@ -210,10 +213,126 @@ def _waypoint_mode_views(net, waypoint_predictor, observations, in_train, genera
     return _waypoint_tail_mode(net, waypoint_predictor, rgb_embedding, depth_embedding, batch_size, in_train, generator, uniforms)
 
 
+# ---- panorama inputs in one launch (csrc/pano_inputs.hip) -----------------------------------------------------------------------
+PINPUTS_ERR_COUNT, PINPUTS_ERR_ANGLE, PINPUTS_ERR_VIEWS = 1, 2, 4     # ETP_PINPUTS_ERR_*
+PANO_INPUT_KEYS = ("rgb_fts", "dep_fts", "loc_fts", "nav_types", "view_lens")   # what forward_panorama takes
+_POPCOUNT12 = np.array([bin(m).count("1") for m in range(1 << NUM_IMGS)], dtype=np.int64)
+_angle_tabs = {}
+
+
+def cand_angle_table() -> torch.Tensor:
+    """[120, 4] fp32 on the host: angle_feature_torch of every heat-map angle, clockwise (Policy_ViewSelection_ETP.py:307, 309); row a
+    holds the bits the per-episode call gives for angle index a"""
+    return angle_feature_torch(torch.arange(NUM_ANGLES).float() / 120 * 2 * math.pi)
+
+
+def _host_cand_tables():
+    """what the fused route hands the simulator side, per heat-map index and built once with the existing route's expressions:
+    cand_angle_fts rows [120,4], counter-clockwise angles (:308) and distances (:310) as Python floats"""
+    if "host" not in _angle_tabs:
+        a120 = torch.arange(NUM_ANGLES)
+        _angle_tabs["host"] = (cand_angle_table(), (2 * math.pi - a120.float() / 120 * 2 * math.pi).tolist(),
+                               ((torch.arange(NUM_CLASSES) + 1) * 0.25).tolist())
+    return _angle_tabs["host"]
+
+
+def _device_angle_tabs(device):
+    key = str(device)
+    if key not in _angle_tabs:
+        _angle_tabs[key] = (cand_angle_table().contiguous().to(device), pano_constants()[1].contiguous().to(device))
+    return _angle_tabs[key]
+
+
+def host_img_idxes(angle: np.ndarray) -> np.ndarray:
+    """counter-clockwise view of every heat-map angle index (:313-314)"""
+    img = 12 - (angle.astype(np.int64) + 5) // 10
+    img[img == 12] = 0
+    return img
+
+
+def host_view_lens(host: np.ndarray, in_train: bool) -> np.ndarray:
+    """view_len of every episode from the host copy of the candidate table [7, B, max_pred]: K + 12 - the distinct candidate views.
+    Vectorised; an episode the kernel would flag (count or angle out of range) gives -1."""
+    count = host[0, :, 0].astype(np.int64)
+    angle = host[5 if in_train else 1].astype(np.int64)
+    B, mp = angle.shape
+    live = np.arange(mp)[None, :] < count[:, None]
+    ok = (count >= 0) & (count <= mp) & ~(live & ((angle < 0) | (angle >= NUM_ANGLES))).any(1)
+    bits = np.where(live & ok[:, None], np.left_shift(1, host_img_idxes(np.clip(angle, 0, NUM_ANGLES - 1))), 0)
+    mask = np.bitwise_or.reduce(bits, axis=1) if mp else np.zeros(B, np.int64)
+    return np.where(ok, count + NUM_IMGS - _POPCOUNT12[mask], -1)
+
+
+def panorama_inputs(rgb_embedding: torch.Tensor, depth_embedding: torch.Tensor, cand: CandidateTable, in_train: bool,
+                    V: Optional[int] = None, host: Optional[np.ndarray] = None) -> dict:
+    """Policy_ViewSelection_ETP.py:289-342 followed by ss_trainer_ETP.py:308-342 (_vp_feature_variable) in one launch of
+    etp_pano_inputs: rgb_embedding [12B, Frgb] and depth_embedding [12B, C, H, W] (clockwise, fp32) and the candidate table ->
+    {rgb_fts [B,V,Frgb], dep_fts [B,V,C], loc_fts [B,V,4], nav_types [B,V] int64, view_lens [B] int64, status [B] int32,
+    cand_img [B,max_pred] int32}, all on the device.  `in_train` picks the sampled angle row of the table, as waypoint_mode does.
+    V=None: the reference's padded length, from `host` (the host copy of cand.table; copied here when absent) -- the outputs have the
+    reference's shapes.  V=int: a capacity (16 always suffices for max_pred = 5); the launch does not depend on a host copy, padding
+    rows are zero and masked by view_lens.  status is left on the device (ETP_PINPUTS_ERR_*): a flagged episode's rows are unwritten."""
+    _require_gpu(rgb_embedding, "panorama_inputs")
+    rgb = rgb_embedding.to(torch.float32).contiguous()
+    dep = depth_embedding.to(device=rgb.device, dtype=torch.float32).contiguous()
+    assert rgb.dim() == 2 and rgb.shape[0] % NUM_IMGS == 0 and dep.dim() >= 2 and dep.shape[0] == rgb.shape[0], (tuple(rgb.shape), tuple(dep.shape))
+    B, Frgb, C = rgb.shape[0] // NUM_IMGS, rgb.shape[1], dep.shape[1]
+    HW = dep[0, 0].numel()
+    table = cand.table
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.shape[:2] == (7, B) and table.device == rgb.device, tuple(table.shape)
+    assert not in_train or cand.sampled, "in_train reads the sampled rows of the table: build it with uniforms"
+    mp = table.shape[2]
+    if V is None:
+        host = table.cpu().numpy() if host is None else host
+        V = max(NUM_IMGS, int(host_view_lens(host, in_train).max()))
+    dev = rgb.device
+    cand_tab, pano_tab = _device_angle_tabs(dev)
+    out = {"rgb_fts": torch.empty(B, V, Frgb, dtype=torch.float32, device=dev), "dep_fts": torch.empty(B, V, C, dtype=torch.float32, device=dev),
+           "loc_fts": torch.empty(B, V, 4, dtype=torch.float32, device=dev), "nav_types": torch.empty(B, V, dtype=torch.int64, device=dev),
+           "view_lens": torch.empty(B, dtype=torch.int64, device=dev), "status": torch.empty(B, dtype=torch.int32, device=dev),
+           "cand_img": torch.empty(B, mp, dtype=torch.int32, device=dev)}
+    check(_lib.lib().etp_pano_inputs(ptr(rgb), ptr(dep), table[0].data_ptr(), table[5 if in_train else 1].data_ptr(), ptr(cand_tab),
+                                     ptr(pano_tab), B, V, mp, Frgb, C, HW, ptr(out["rgb_fts"]), ptr(out["dep_fts"]), ptr(out["loc_fts"]),
+                                     ptr(out["nav_types"]), ptr(out["view_lens"]), ptr(out["cand_img"]), ptr(out["status"]), _stream()),
+          "etp_pano_inputs")
+    return out
+
+
+def _fused_tail_outputs(net, rgb_embedding, depth_embedding, cand, host, in_train):
+    """the output dict of mode='waypoint' with ETP.fuse_pano_inputs: the simulator side's host values from the table copy, and the
+    planner's inputs from one launch; cand_rgb / cand_depth / pano_rgb / pano_depth are not built"""
+    count = host[0, :, 0]
+    angle, dist = host[5 if in_train else 1].astype(np.int64), host[6 if in_train else 2].astype(np.int64)
+    lens = host_view_lens(host, in_train)
+    if (lens < 0).any():
+        raise _lib.EtpError(f"the candidate table of episodes {np.nonzero(lens < 0)[0].tolist()} is malformed (count outside 0 .. "
+                            f"{angle.shape[1]} or an angle outside 0 .. 119)")
+    V = getattr(net, "pano_inputs_capacity", None)
+    if V is not None and int(lens.max()) > V:
+        raise ValueError(f"pano_inputs_capacity={V} < the longest view list {int(lens.max())}")
+    V = max(NUM_IMGS, int(lens.max())) if V is None else V   # None: the reference's padded length
+    # launched first: the device works while the host builds the lists below (the embeddings in the shapes the existing route reads
+    # them in, its two reshapes before the pools)
+    pano = panorama_inputs(rgb_embedding.reshape(-1, 512), depth_embedding.reshape(-1, 128, 4, 4), cand, in_train, V=V)
+    angle_fts, angles_cc, dists = _host_cand_tables()
+    img = host_img_idxes(angle)
+    ks = count.tolist()
+    return {
+        "cand_angle_fts": [angle_fts[angle[j, :n]] for j, n in enumerate(ks)],
+        "cand_img_idxes": [img[j, :n].copy() for j, n in enumerate(ks)],
+        "cand_angles": [[angles_cc[a] for a in angle[j, :n].tolist()] for j, n in enumerate(ks)],
+        "cand_distances": [[dists[d] for d in dist[j, :n].tolist()] for j, n in enumerate(ks)],
+        "pano_angle_fts": deepcopy(net.pano_angle_fts), "pano_img_idxes": deepcopy(net.pano_img_idxes),
+        "pano_inputs": pano,
+    }
+
+
 def _waypoint_tail_mode(net, waypoint_predictor, rgb_embedding, depth_embedding, batch_size, in_train, generator, uniforms):
     logits = waypoint_predictor(rgb_embedding, depth_embedding)
     cand = waypoint_predictor.candidates(logits, in_train, generator=generator, uniforms=uniforms)
     host = cand.table.cpu().numpy()                       # the one device-to-host copy of the call
+    if getattr(net, "fuse_pano_inputs", False):
+        return _fused_tail_outputs(net, rgb_embedding, depth_embedding, cand, host, in_train)
 
     # back to counter-clockwise (:201-213) and the two average pools (:289-290)
     rgb_r = rgb_embedding.reshape(batch_size, NUM_IMGS, 512, 1, 1)

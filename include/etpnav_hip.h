@@ -999,6 +999,37 @@ int etp_pano_store_fwd(const float* pano_embeds, const uint8_t* pano_masks, cons
 int etp_pano_store_bwd(const float* d_store, const uint8_t* pano_masks, const int64_t* nav_types, const int32_t* row_base,
                        const int32_t* n_cand, int B, int V, int H, int R, float* d_pano_embeds, int accumulate, etp_stream_t stream);
 
+/* The panorama encoder's inputs from the waypoint head's candidate table (csrc/pano_inputs.hip): the end of ETP.forward(mode='waypoint')
+ * (vlnce_baselines/models/Policy_ViewSelection_ETP.py:289-342) followed by RLTrainer._vp_feature_variable
+ * (vlnce_baselines/ss_trainer_ETP.py:308-342), one launch, one wavefront per output row.
+ *   rgb_embedding [12B, Frgb] and depth_embedding [12B, C, HW] fp32: the view encoders' outputs, CLOCKWISE (episode b's
+ *   counter-clockwise view i is row b*12 + (12 - i) % 12, Policy_ViewSelection_ETP.py:182-190, 201-213).  cand_count: the count of
+ *   episode b at cand_count[b * max_pred] (column 0 of row 0 of etp_waypoint_tail's table); cand_angle [B, max_pred]: the table's angle
+ *   row (eval) or sampled-angle row (in_train); the distances play no part in these outputs.  cand_angle_tab [120,4] and
+ *   pano_angle_tab [12,4] fp32: angle_feature_torch of the 120 heat-map angles and of the 12 panorama headings (:141-143), built once on
+ *   the host -- the kernel has no transcendental.
+ * For episode b with K = count, a_j = angle j, img(a) = 12 - (a + 5) / 10 with 12 -> 0 (:313-314), mask = the views img(a_j),
+ * view_len = K + 12 - popcount(mask):
+ *     row v < K             candidate v, in table order: view i = img(a_v), nav_types 1, loc_fts = cand_angle_tab[a_v];
+ *     row K <= v < view_len the (v - K)-th view i of 0 .. 11 that is not in the mask: nav_types 0, loc_fts = pano_angle_tab[i];
+ *       rgb_fts [B,V,Frgb]  a bit copy of rgb_embedding's row of view i (the 1 x 1 pool),
+ *       dep_fts [B,V,C]     per channel the HW values of view i added in index order into one fp32 accumulator, then one division by HW;
+ *     row v >= view_len     exact zeros in rgb_fts, dep_fts, loc_fts [B,V,4] and nav_types [B,V] (int64);
+ *   view_lens [B] int64, cand_img [B, max_pred] int32 (img(a_j), -1 beyond K), status [B] int32.
+ * status[b] = 0, or the OR of ETP_PINPUTS_ERR_COUNT (count outside 0 .. max_pred; the angles are then not read), ETP_PINPUTS_ERR_ANGLE (an
+ * angle outside 0 .. 119), ETP_PINPUTS_ERR_VIEWS (view_len > V): a flagged episode writes its status and nothing else, and nothing is
+ * indexed by its values.  Plain vector stores, no atomics, no LDS, no scratch; a second run gives the same bits.
+ * ETP_ERR_INVALID before anything is launched: a NULL operand, B < 1, V < 12, max_pred < 1, Frgb < 4 or not a multiple of 4, C < 1,
+ * HW < 1, rgb_embedding / depth_embedding / rgb_fts not 16-byte aligned, nav_types / view_lens not 8-byte or any other operand not
+ * 4-byte aligned. */
+#define ETP_PINPUTS_ERR_COUNT 1
+#define ETP_PINPUTS_ERR_ANGLE 2
+#define ETP_PINPUTS_ERR_VIEWS 4
+int etp_pano_inputs(const float* rgb_embedding, const float* depth_embedding, const int32_t* cand_count, const int32_t* cand_angle,
+                    const float* cand_angle_tab, const float* pano_angle_tab, int B, int V, int max_pred, int Frgb, int C, int HW,
+                    float* rgb_fts, float* dep_fts, float* loc_fts, int64_t* nav_types, int64_t* view_lens, int32_t* cand_img,
+                    int32_t* status, etp_stream_t stream);
+
 /* Pre-training MLM task for a planner created with cfg.use_lang2visn = 1:
  * GlocalTextPathCMT.forward_mlm (pretrain vilmodel.py:708-754): the text (output of etp_txt_fwd) attends to the graph-node
  * inputs gmap_img_fts + step + position embeddings through forward_lang2visn of every x-layer (:400-411), then
