@@ -1,0 +1,188 @@
+// A pre-training batch's device side, straight from the resident view-feature store: two launches.
+//
+// traj_views_kernel replaces, per batch, R2RTextPathData.get_traj_pano_fts (pretrain_src/pretrain_src/data/dataset.py:483-526: per
+// trajectory step the candidate views in scanvp_cands order, then the panorama views no candidate names, in index order) followed by
+// the padding of sap_collate / mlm_collate (tasks.py:331-343, 107-120) and the slice x[:, :image_feat_size] of get_input
+// (dataset.py:453-454).  traj_pair_dists_kernel replaces the double loop of get_gmap_inputs (dataset.py:316-320) and the padding of
+// tasks.py:350-355.  The host hands over indices and scalars only (etpnav_amd/pretrain_data.py); no feature row crosses the bus.
+//
+// Both follow pano_inputs.hip: one wavefront per output row, the width a run-time value, each lane owning groups of 4 consecutive
+// columns 256 apart (16-byte accesses) in the feature copies.  Every wave derives its step's (its sample's) record and every malformed
+// condition for itself from uniform loads -- no LDS, no barrier, no atomics, plain stores -- and nothing of a malformed step or sample
+// is indexed.  No transcendental: the angle features come from the host.  The distance is ONE double division rounded once to fp32;
+// the file is compiled with -ffp-contract=off (build.py), as gmap_update.hip is.
+#include "kernels.h"
+
+namespace etp {
+
+struct TrajCand {
+  unsigned long long mask;   // bit i: a candidate names view i
+  int k, len, err;
+};
+
+// every lane of the wave returns the same record
+__device__ __forceinline__ TrajCand traj_cand(const int32_t* pano_row, const int32_t* count, const int32_t* view, int r, int V, int Kmax,
+                                              int P, int N) {
+  TrajCand c;
+  c.k = count[r];
+  c.mask = 0;
+  c.len = 0;
+  c.err = (c.k < 0 || c.k > Kmax) ? ETP_TRAJ_ERR_COUNT : 0;
+  const int row = pano_row[r];
+  if (row < 0 || row >= N) c.err |= ETP_TRAJ_ERR_ROW;
+  if (c.err & ETP_TRAJ_ERR_COUNT) return c;
+  for (int j = 0; j < c.k; ++j) {
+    const int i = view[(long)r * Kmax + j];
+    if (i < 0 || i >= P) c.err |= ETP_TRAJ_ERR_VIEW;
+    else c.mask |= 1ull << i;
+  }
+  c.len = c.k + P - __popcll(c.mask);                      // two candidates of one view free that view once: the length can exceed P
+  if (c.len > V) c.err |= ETP_TRAJ_ERR_VIEWS;
+  return c;
+}
+
+// grid ceil(R * V / 4) blocks of four waves: wave w writes row (r, v) = (w / V, w % V) of the three feature tensors and of nav_types;
+// the wave of v == 0 also writes the step's status and view length
+__global__ __launch_bounds__(256) void traj_views_kernel(const float* __restrict__ img, const float* __restrict__ dep,
+                                                         const int32_t* __restrict__ pano_row, const int32_t* __restrict__ count,
+                                                         const int32_t* __restrict__ view, const float* __restrict__ cand_loc,
+                                                         const float* __restrict__ view_loc_tab, int R, int V, int Kmax, int P, int Fimg,
+                                                         int ld_img, int Fdep, int ld_dep, int N, float* __restrict__ rgb_fts,
+                                                         float* __restrict__ dep_fts, float* __restrict__ loc_fts,
+                                                         int64_t* __restrict__ nav_types, int64_t* __restrict__ view_lens,
+                                                         int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long)R * V) return;
+  const int r = (int)(row / V), v = (int)(row % V);
+  const TrajCand c = traj_cand(pano_row, count, view, r, V, Kmax, P, N);
+  if (v == 0 && lane == 0) status[r] = c.err;
+  if (c.err) return;
+  if (v == 0 && lane == 0) view_lens[r] = c.len;
+  float* drgb = rgb_fts + row * Fimg;
+  float* ddep = dep ? dep_fts + row * Fdep : nullptr;
+  if (v >= c.len) {                                        // padding: exact zeros (pad_tensors / pad_sequence)
+    const float z[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int f = lane * 4; f < Fimg; f += 256) store4(drgb + f, z);
+    if (dep)
+      for (int f = lane * 4; f < Fdep; f += 256) store4(ddep + f, z);
+    if (lane < 4) loc_fts[row * 4 + lane] = 0.f;
+    if (lane == 0) nav_types[row] = 0;
+    return;
+  }
+  int i;
+  const float* loc;
+  if (v < c.k) {                                           // candidate v, in table order
+    i = view[(long)r * Kmax + v];
+    loc = cand_loc + ((long)r * Kmax + v) * 4;
+  } else {                                                 // the (v - k)-th view, in index order, that no candidate names
+    unsigned long long free = ~c.mask;
+    if (P < 64) free &= (1ull << P) - 1;
+    for (int j = c.k; j < v; ++j) free &= free - 1;
+    i = __ffsll(free) - 1;
+    loc = view_loc_tab + i * 4;
+  }
+  const long src = (long)pano_row[r] * P + i;
+  const float* simg = img + src * ld_img;
+  for (int f = lane * 4; f < Fimg; f += 256) {             // x[:, :image_feat_size]: the first Fimg of ld_img columns
+    float t[4];
+    load4(simg + f, t);
+    store4(drgb + f, t);
+  }
+  if (dep) {
+    const float* sdep = dep + src * ld_dep;
+    for (int f = lane * 4; f < Fdep; f += 256) {
+      float t[4];
+      load4(sdep + f, t);
+      store4(ddep + f, t);
+    }
+  }
+  if (lane < 4) loc_fts[row * 4 + lane] = loc[lane];
+  if (lane == 0) nav_types[row] = v < c.k ? 1 : 0;
+}
+
+// grid ceil(B * G / 4) blocks of four waves: wave w writes row (b, i) = (w / G, w % G) of gmap_pair_dists and gmap_masks[b, i]; the wave
+// of i == 0 also writes the sample's status.  Every wave checks the whole sample: lane l looks at entries l, l + 64, ..
+__global__ __launch_bounds__(256) void traj_pair_dists_kernel(const double* __restrict__ dist, int64_t dist_len,
+                                                              const int64_t* __restrict__ scan_off, const int32_t* __restrict__ scan_n,
+                                                              const int32_t* __restrict__ gmap_idx, const int32_t* __restrict__ gmap_len,
+                                                              int B, int G, float* __restrict__ pair, uint8_t* __restrict__ masks,
+                                                              int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long)B * G) return;
+  const int b = (int)(row / G), i = (int)(row % G);
+  const int len = gmap_len[b], n = scan_n[b];
+  const int64_t off = scan_off[b];
+  const int32_t* idx = gmap_idx + (long)b * G;
+  int err = (len < 1 || len > G) ? ETP_TRAJ_ERR_LEN : 0;
+  if (n < 1 || off < 0 || off > dist_len || (int64_t)n * n > dist_len - off) err |= ETP_TRAJ_ERR_SCAN;
+  if (!err) {
+    int bad = 0;
+    for (int j = 1 + lane; j < len; j += 64) bad |= (idx[j] < 0 || idx[j] >= n);   // entry 0 is [stop]: never looked up
+    if (__any(bad)) err = ETP_TRAJ_ERR_INDEX;
+  }
+  if (i == 0 && lane == 0) status[b] = err;
+  if (err) return;
+  if (lane == 0) masks[row] = i < len ? 1 : 0;
+  float* out = pair + row * G;
+  const bool live = i >= 1 && i < len;
+  const int vi = live ? idx[i] : 0;
+  for (int j = lane; j < G; j += 64) {
+    float d = 0.f;
+    if (live && j >= 1 && j < len && j != i) {
+      // the reference fills (i, j) and (j, i), i < j, from shortest_distances[vp_i][vp_j]: the lookup is directional
+      const int vj = idx[j];
+      const int a = i < j ? vi : vj, c = i < j ? vj : vi;
+      d = (float)(dist[off + (int64_t)a * n + c] / 30.0);
+    }
+    out[j] = d;
+  }
+}
+
+}  // namespace etp
+
+extern "C" int etp_traj_views(const float* img_store, const float* dep_store, const int32_t* pano_row, const int32_t* cand_count,
+                              const int32_t* cand_view, const float* cand_loc, const float* view_loc_tab, int R, int V, int Kmax, int P,
+                              int F_img, int ld_img, int F_dep, int ld_dep, int N, float* rgb_fts, float* dep_fts, float* loc_fts,
+                              int64_t* nav_types, int64_t* view_lens, int32_t* status, etp_stream_t stream) {
+  using namespace etp;
+  ETP_REQUIRE(img_store && pano_row && cand_count && cand_view && cand_loc && view_loc_tab && rgb_fts && loc_fts && nav_types &&
+                  view_lens && status, "null pointer");
+  ETP_REQUIRE((dep_store == nullptr) == (dep_fts == nullptr), "dep_store and dep_fts are given together or both NULL");
+  ETP_REQUIRE(R >= 1 && V >= 1 && N >= 1, "R, V and N are positive");
+  ETP_REQUIRE(Kmax >= 1 && Kmax <= 64 && P >= 1 && P <= 64, "Kmax and P lie in 1 .. 64");
+  ETP_REQUIRE(F_img >= 4 && F_img % 4 == 0 && ld_img % 4 == 0 && F_img <= ld_img, "F_img and ld_img are multiples of 4, 4 <= F_img <= ld_img");
+  ETP_REQUIRE(!dep_store || (F_dep >= 4 && F_dep % 4 == 0 && ld_dep % 4 == 0 && F_dep <= ld_dep),
+              "F_dep and ld_dep are multiples of 4, 4 <= F_dep <= ld_dep");
+  ETP_REQUIRE((long)R * V <= 0x7FFFFFFFL / 4, "R * V rows exceed the grid");
+  ETP_REQUIRE(((uintptr_t)img_store | (uintptr_t)dep_store | (uintptr_t)rgb_fts | (uintptr_t)dep_fts) % 16 == 0,
+              "img_store, dep_store, rgb_fts and dep_fts must be 16-byte aligned");
+  ETP_REQUIRE(((uintptr_t)nav_types | (uintptr_t)view_lens) % 8 == 0, "nav_types and view_lens must be 8-byte aligned");
+  ETP_REQUIRE(((uintptr_t)pano_row | (uintptr_t)cand_count | (uintptr_t)cand_view | (uintptr_t)cand_loc | (uintptr_t)view_loc_tab |
+               (uintptr_t)loc_fts | (uintptr_t)status) % 4 == 0, "fp32 and int32 operands must be 4-byte aligned");
+  const long rows = (long)R * V;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  ETP_LAUNCH(traj_views_kernel, grid, block, 0, (hipStream_t)stream, img_store, dep_store, pano_row, cand_count, cand_view, cand_loc,
+             view_loc_tab, R, V, Kmax, P, F_img, ld_img, F_dep, ld_dep, N, rgb_fts, dep_fts, loc_fts, nav_types, view_lens, status);
+  ETP_CHECK_LAUNCH("traj_views");
+  return ETP_OK;
+}
+
+extern "C" int etp_traj_pair_dists(const double* dist_tab, int64_t dist_len, const int64_t* scan_off, const int32_t* scan_n,
+                                   const int32_t* gmap_idx, const int32_t* gmap_len, int B, int G, float* gmap_pair_dists,
+                                   uint8_t* gmap_masks, int32_t* status, etp_stream_t stream) {
+  using namespace etp;
+  ETP_REQUIRE(dist_tab && scan_off && scan_n && gmap_idx && gmap_len && gmap_pair_dists && gmap_masks && status, "null pointer");
+  ETP_REQUIRE(B >= 1 && G >= 1 && dist_len >= 1, "B, G and dist_len are positive");
+  ETP_REQUIRE((long)B * G <= 0x7FFFFFFFL / 4, "B * G rows exceed the grid");
+  ETP_REQUIRE(((uintptr_t)dist_tab | (uintptr_t)scan_off) % 8 == 0, "dist_tab and scan_off must be 8-byte aligned");
+  ETP_REQUIRE(((uintptr_t)scan_n | (uintptr_t)gmap_idx | (uintptr_t)gmap_len | (uintptr_t)gmap_pair_dists | (uintptr_t)status) % 4 == 0,
+              "fp32 and int32 operands must be 4-byte aligned");
+  const long rows = (long)B * G;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  ETP_LAUNCH(traj_pair_dists_kernel, grid, block, 0, (hipStream_t)stream, dist_tab, dist_len, scan_off, scan_n, gmap_idx, gmap_len, B, G,
+             gmap_pair_dists, gmap_masks, status);
+  ETP_CHECK_LAUNCH("traj_pair_dists");
+  return ETP_OK;
+}

@@ -1030,6 +1030,51 @@ int etp_pano_inputs(const float* rgb_embedding, const float* depth_embedding, co
                     float* rgb_fts, float* dep_fts, float* loc_fts, int64_t* nav_types, int64_t* view_lens, int32_t* cand_img,
                     int32_t* status, etp_stream_t stream);
 
+/* A pre-training batch's device side from the resident view-feature store (csrc/traj_batch.hip; host side etpnav_amd/pretrain_data.py).
+ * etp_traj_views, one launch, one wavefront per output row: R2RTextPathData.get_traj_pano_fts
+ *   (pretrain_src/pretrain_src/data/dataset.py:483-526) plus the padding of sap_collate / mlm_collate (tasks.py:331-343) for R trajectory
+ *   steps.  img_store [N, P, ld_img] and dep_store [N, P, ld_dep] fp32 (dep_store NULL: no depth, dep_fts NULL too, F_dep / ld_dep
+ *   unread); per step r: pano_row [R] the store row, cand_count [R], cand_view [R, Kmax] view indices, cand_loc [R, Kmax, 4] the
+ *   candidates' angle features (host); view_loc_tab [P, 4] the angle features of get_view_rel_angles(12).  All indices int32.
+ *   For step r with k = count, mask = the views cand_view[r, 0 .. k-1], view_len = k + P - popcount(mask) (two candidates of one view
+ *   free that view once, so view_len can exceed P):
+ *     row v < k              candidate v, in table order: view i = cand_view[r, v], nav_types 1, loc_fts = cand_loc[r, v];
+ *     row k <= v < view_len  the (v - k)-th view i of 0 .. P-1 that is not in the mask: nav_types 0, loc_fts = view_loc_tab[i];
+ *       rgb_fts [R,V,F_img]  a bit copy of the first F_img columns of img_store[pano_row[r], i] (x[:, :image_feat_size]),
+ *       dep_fts [R,V,F_dep]  likewise from dep_store;
+ *     row v >= view_len      exact zeros in rgb_fts, dep_fts, loc_fts [R,V,4] and nav_types [R,V] (int64);
+ *   view_lens [R] int64, status [R] int32 = 0, or the OR of ETP_TRAJ_ERR_COUNT (count outside 0 .. Kmax; the views are then not
+ *   read), ETP_TRAJ_ERR_VIEW (a view index outside 0 .. P-1), ETP_TRAJ_ERR_ROW (pano_row outside 0 .. N-1), ETP_TRAJ_ERR_VIEWS
+ *   (view_len > V): a flagged step writes its status and nothing else, and nothing is indexed by its values.
+ *   ETP_ERR_INVALID before anything is launched: a NULL operand (dep_store and dep_fts only together), R, V or N < 1, Kmax or P outside
+ *   1 .. 64, F_img (F_dep) < 4, not a multiple of 4 or > ld_img (ld_dep), ld_img (ld_dep) not a multiple of 4, img_store / dep_store /
+ *   rgb_fts / dep_fts not 16-byte aligned, nav_types / view_lens not 8-byte or any other operand not 4-byte aligned.
+ * etp_traj_pair_dists, one launch, one wavefront per output row: the double loop of get_gmap_inputs (dataset.py:316-320) plus the
+ *   padding of tasks.py:350-355 for B samples.  dist_tab: dist_len float64, one n x n block per scan with entry [a][b] the Dijkstra
+ *   distance from a to b; scan_off [B] int64 and scan_n [B] int32 the sample's block; gmap_idx [B, G] int32 the local viewpoint index
+ *   (entry 0, [stop], is never looked up); gmap_len [B] int32.  For 1 <= i < j < len:
+ *     gmap_pair_dists[b, i, j] = gmap_pair_dists[b, j, i] = (float)(dist_tab[off + idx_i * n + idx_j] / 30.0), evaluated in double and
+ *     rounded once (the lookup is directional, as the reference's is); row 0, column 0, the diagonal and the padding are exact zeros;
+ *   gmap_masks [B, G] u8 = (i < len).  status [B] int32 = 0, or ETP_TRAJ_ERR_LEN (gmap_len outside 1 .. G), ETP_TRAJ_ERR_SCAN (the
+ *   block does not lie in the table), ETP_TRAJ_ERR_INDEX (an index of 1 .. len-1 outside 0 .. n-1): a flagged sample writes its status
+ *   and nothing else.  ETP_ERR_INVALID before anything is launched: a NULL operand, B, G or dist_len < 1, dist_tab / scan_off not
+ *   8-byte or scan_n / gmap_idx / gmap_len / gmap_pair_dists / status not 4-byte aligned.
+ * Plain vector stores, no atomics, no LDS, no scratch; a second run gives the same bits. */
+#define ETP_TRAJ_ERR_COUNT 1
+#define ETP_TRAJ_ERR_VIEW 2
+#define ETP_TRAJ_ERR_ROW 4
+#define ETP_TRAJ_ERR_VIEWS 8
+#define ETP_TRAJ_ERR_LEN 1
+#define ETP_TRAJ_ERR_SCAN 2
+#define ETP_TRAJ_ERR_INDEX 4
+int etp_traj_views(const float* img_store, const float* dep_store, const int32_t* pano_row, const int32_t* cand_count,
+                   const int32_t* cand_view, const float* cand_loc, const float* view_loc_tab, int R, int V, int Kmax, int P, int F_img,
+                   int ld_img, int F_dep, int ld_dep, int N, float* rgb_fts, float* dep_fts, float* loc_fts, int64_t* nav_types,
+                   int64_t* view_lens, int32_t* status, etp_stream_t stream);
+int etp_traj_pair_dists(const double* dist_tab, int64_t dist_len, const int64_t* scan_off, const int32_t* scan_n, const int32_t* gmap_idx,
+                        const int32_t* gmap_len, int B, int G, float* gmap_pair_dists, uint8_t* gmap_masks, int32_t* status,
+                        etp_stream_t stream);
+
 /* Pre-training MLM task for a planner created with cfg.use_lang2visn = 1:
  * GlocalTextPathCMT.forward_mlm (pretrain vilmodel.py:708-754): the text (output of etp_txt_fwd) attends to the graph-node
  * inputs gmap_img_fts + step + position embeddings through forward_lang2visn of every x-layer (:400-411), then
