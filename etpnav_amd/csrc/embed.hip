@@ -787,15 +787,7 @@ __global__ __launch_bounds__(256) void scale_f32_kernel(float* __restrict__ p, l
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] *= scale;
 }
 
-// ---- host launchers -------------------------------------------------------------------
-#define ETP_DISPATCH_H(H, CALL)                                                         \
-  switch ((H) / 256) {                                                                  \
-    case 1: { constexpr int NCH = 1; CALL; } break;                                     \
-    case 2: { constexpr int NCH = 2; CALL; } break;                                     \
-    case 3: { constexpr int NCH = 3; CALL; } break;                                     \
-    default: return fail(ETP_ERR_INVALID, "hidden size must be 256, 512 or 768");       \
-  }
-
+// ---- host launchers (ETP_DISPATCH_H: row.h) -------------------------------------------
 static inline int row_grid(int M, int cap) { return (int)std::min<long>(((long)M + 3) / 4, cap); }
 
 // Activations that cross kernels of the "residual stream" are fp32 (y / dy below); `yt` / `xt` are optional copies in

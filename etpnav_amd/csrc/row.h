@@ -31,3 +31,12 @@ template <int NCH> __device__ __forceinline__ void row_zero(Row<NCH>& a) {
 }
 
 }  // namespace etp
+
+// CALL with `constexpr int NCH = H / 256` in scope; inside namespace etp or behind `using namespace etp`
+#define ETP_DISPATCH_H(H, CALL)                                                         \
+  switch ((H) / 256) {                                                                  \
+    case 1: { constexpr int NCH = 1; CALL; } break;                                     \
+    case 2: { constexpr int NCH = 2; CALL; } break;                                     \
+    case 3: { constexpr int NCH = 3; CALL; } break;                                     \
+    default: return fail(ETP_ERR_INVALID, "hidden size must be 256, 512 or 768");       \
+  }

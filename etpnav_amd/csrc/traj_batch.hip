@@ -11,7 +11,11 @@
 // condition for itself from uniform loads -- no LDS, no barrier, no atomics, plain stores -- and nothing of a malformed step or sample
 // is indexed.  No transcendental: the angle features come from the host.  The distance is ONE double division rounded once to fp32;
 // the file is compiled with -ffp-contract=off (build.py), as gmap_update.hip is.
+//
+// traj_nodes_fwd_kernel / traj_nodes_bwd_kernel (below) turn the panorama embeddings of those steps into the node features and back
+// from the same kind of tables, in the same idiom, on H-wide rows (row.h).
 #include "kernels.h"
+#include "row.h"
 
 namespace etp {
 
@@ -140,7 +144,234 @@ __global__ __launch_bounds__(256) void traj_pair_dists_kernel(const double* __re
   }
 }
 
+// ---- trajectory node features from the same integer tables: GlobalMapEncoder._aggregate_gmap_features (vilmodel.py:585-619) ----------
+// What graph_inputs.pack_traj_csr + gather_sum_kernel (embed.hip) compute, without the CSR: every wave finds its row's sources in the
+// sample's tables by uniform loads and ballots, and adds them in the CSR's order with gather_sum_kernel's operation, one fused
+// multiply-add per element (this file is built with -ffp-contract=off, so it is spelled out), from +0.
+
+struct TrajSample {
+  int t0, t1, len, err;
+};
+
+// sample b's step range and node count, and every malformed condition of its steps; every lane returns the same record
+__device__ __forceinline__ TrajSample traj_sample(const int32_t* step_off, const int64_t* view_lens, const int32_t* count,
+                                                  const int32_t* gmap_len, int b, int R, int V, int Kmax, int G, int lane) {
+  TrajSample s;
+  s.t0 = step_off[b];
+  s.t1 = step_off[b + 1];
+  s.len = gmap_len[b];
+  s.err = (s.len < 1 || s.len > G) ? ETP_TRAJ_ERR_LEN : 0;
+  if (s.t0 < 0 || s.t1 > R || s.t1 <= s.t0) {
+    s.err |= ETP_TRAJ_ERR_STEPS;
+    return s;
+  }
+  int bad_k = 0, bad_n = 0;
+  for (int t = s.t0 + lane; t < s.t1; t += 64) {
+    const int k = count[t];
+    const int64_t n = view_lens[t];
+    bad_k |= (k < 0 || k > Kmax);
+    bad_n |= (n < 1 || n > V);
+  }
+  if (__any(bad_k)) s.err |= ETP_TRAJ_ERR_COUNT;
+  if (__any(bad_n)) s.err |= ETP_TRAJ_ERR_VIEWS;
+  return s;
+}
+
+// the last step of [t0, t1) at viewpoint id, or -1
+__device__ __forceinline__ int traj_last_visit(const int32_t* step_vp, int t0, int t1, int id, int lane) {
+  int last = -1;
+  for (int base = t0; base < t1; base += 64) {
+    const int t = base + lane;
+    const unsigned long long m = __ballot(t < t1 && step_vp[t] == id);
+    if (m) last = base + 63 - __clzll(m);
+  }
+  return last;
+}
+
+// bit j: slot j of step t names id (Kmax <= 64: one lane per slot)
+__device__ __forceinline__ unsigned long long traj_slots(const int32_t* count, const int32_t* cand_vp, int t, int Kmax, int id, int lane) {
+  return __ballot(lane < count[t] && cand_vp[(long)t * Kmax + lane] == id);
+}
+
+__device__ __forceinline__ int traj_slot_count(const int32_t* count, const int32_t* cand_vp, int t0, int t1, int Kmax, int id, int lane) {
+  int n = 0;
+  for (int t = t0; t < t1; ++t) n += __popcll(traj_slots(count, cand_vp, t, Kmax, id, lane));
+  return n;
+}
+
+// the first g of 1 .. len-1 with gmap_id[b, g] == id, or 0
+__device__ __forceinline__ int traj_node_of(const int32_t* ids, int len, int id, int lane) {
+  for (int base = 1; base < len; base += 64) {
+    const int g = base + lane;
+    const unsigned long long m = __ballot(g < len && ids[g] == id);
+    if (m) return base + __ffsll(m) - 1;
+  }
+  return 0;
+}
+
+template <int NCH> __device__ __forceinline__ void row_fma(Row<NCH>& acc, float w, const Row<NCH>& x) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc.v[c][e] = fmaf(w, x.v[c][e], acc.v[c][e]);
+}
+
+__device__ __forceinline__ float traj_weight(long n) { return (float)(1.0 / (double)n); }   // torch.tensor(1.0 / n, dtype=float32)
+
+// grid ceil(B * G / 4) blocks of four waves: wave w writes node row (b, g) = (w / G, w % G) and its status word
+template <int NCH>
+__global__ __launch_bounds__(256) void traj_nodes_fwd_kernel(const float* __restrict__ pano, const int32_t* __restrict__ step_off,
+                                                             const int32_t* __restrict__ step_vp, const int64_t* __restrict__ view_lens,
+                                                             const int32_t* __restrict__ count, const int32_t* __restrict__ cand_vp,
+                                                             const int32_t* __restrict__ gmap_id, const int32_t* __restrict__ gmap_len,
+                                                             int B, int R, int V, int Kmax, int G, float* __restrict__ out,
+                                                             int32_t* __restrict__ status) {
+  constexpr int H = NCH * 256;
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long)B * G) return;
+  const int b = (int)(row / G), g = (int)(row % G);
+  const TrajSample s = traj_sample(step_off, view_lens, count, gmap_len, b, R, V, Kmax, G, lane);
+  if (s.err) {
+    if (lane == 0) status[row] = s.err;
+    return;
+  }
+  Row<NCH> acc, x;
+  row_zero<NCH>(acc);
+  int err = 0;
+  if (g >= 1 && g < s.len) {
+    const int id = gmap_id[row];
+    const int last = id < 0 ? -1 : traj_last_visit(step_vp, s.t0, s.t1, id, lane);
+    if (last >= 0) {                                       // visited: the mean of the valid views of its last visit
+      const int n = (int)view_lens[last];
+      const float w = traj_weight(n);
+      for (int j = 0; j < n; ++j) {
+        row_load<NCH>(x, pano + ((long)last * V + j) * H, lane);
+        row_fma<NCH>(acc, w, x);
+      }
+    } else {                                               // a ghost: the mean over the slots that name it
+      const int cnt = id < 0 ? 0 : traj_slot_count(count, cand_vp, s.t0, s.t1, Kmax, id, lane);
+      if (cnt == 0) err = ETP_TRAJ_ERR_NODE;
+      else {
+        const float w = traj_weight(cnt);
+        for (int t = s.t0; t < s.t1; ++t) {
+          const int n = (int)view_lens[t];
+          unsigned long long m = traj_slots(count, cand_vp, t, Kmax, id, lane);
+          if (n < 64) m &= (1ull << n) - 1;                // a slot beyond the valid views counted above and adds nothing
+          for (; m; m &= m - 1) {
+            row_load<NCH>(x, pano + ((long)t * V + (__ffsll(m) - 1)) * H, lane);
+            row_fma<NCH>(acc, w, x);
+          }
+        }
+      }
+    }
+  }
+  if (lane == 0) status[row] = err;
+  if (!err) row_store<NCH>(acc, out + row * H, lane);
+}
+
+// grid ceil(R * V / 4) blocks of four waves: wave w writes panorama row (r, j) = (w / V, w % V); the wave of j == 0 also the step's status
+template <int NCH>
+__global__ __launch_bounds__(256) void traj_nodes_bwd_kernel(const float* __restrict__ dg, const int32_t* __restrict__ step_off,
+                                                             const int32_t* __restrict__ step_vp, const int64_t* __restrict__ view_lens,
+                                                             const int32_t* __restrict__ count, const int32_t* __restrict__ cand_vp,
+                                                             const int32_t* __restrict__ gmap_id, const int32_t* __restrict__ gmap_len,
+                                                             int B, int R, int V, int Kmax, int G, float* __restrict__ d_pano,
+                                                             int32_t* __restrict__ status) {
+  constexpr int H = NCH * 256;
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long)R * V) return;
+  const int r = (int)(row / V), j = (int)(row % V);
+  // the step's sample: the one b with step_off[b] <= r < step_off[b+1]
+  int b = -1, owners = 0;
+  for (int base = 0; base < B; base += 64) {
+    const int c = base + lane;
+    const unsigned long long m = __ballot(c < B && step_off[c] <= r && r < step_off[c + 1]);
+    if (m) {
+      if (b < 0) b = base + __ffsll(m) - 1;
+      owners += __popcll(m);
+    }
+  }
+  TrajSample s;
+  s.err = ETP_TRAJ_ERR_STEPS;
+  if (owners == 1) s = traj_sample(step_off, view_lens, count, gmap_len, b, R, V, Kmax, G, lane);
+  if (j == 0 && lane == 0) status[r] = s.err;
+  if (s.err) return;
+  const int n = (int)view_lens[r];
+  const int32_t* ids = gmap_id + (long)b * G;
+  int ga = 0, gb = 0;
+  float wa = 0.f, wb = 0.f;
+  if (j < n) {
+    const int ida = step_vp[r];
+    if (ida >= 0 && traj_last_visit(step_vp, s.t0, s.t1, ida, lane) == r) {                  // (A)
+      ga = traj_node_of(ids, s.len, ida, lane);
+      wa = traj_weight(n);
+    }
+    if (j < count[r]) {                                                                      // (B)
+      const int idb = cand_vp[(long)r * Kmax + j];
+      if (idb >= 0 && traj_last_visit(step_vp, s.t0, s.t1, idb, lane) < 0) {
+        gb = traj_node_of(ids, s.len, idb, lane);
+        if (gb) wb = traj_weight(traj_slot_count(count, cand_vp, s.t0, s.t1, Kmax, idb, lane));
+      }
+    }
+  }
+  Row<NCH> acc, x;
+  row_zero<NCH>(acc);
+  const float* base = dg + (long)b * G * H;
+  const bool a_first = ga && (!gb || ga < gb);
+  if (a_first) {
+    row_load<NCH>(x, base + (long)ga * H, lane);
+    row_fma<NCH>(acc, wa, x);
+  }
+  if (gb) {
+    row_load<NCH>(x, base + (long)gb * H, lane);
+    row_fma<NCH>(acc, wb, x);
+  }
+  if (ga && !a_first) {
+    row_load<NCH>(x, base + (long)ga * H, lane);
+    row_fma<NCH>(acc, wa, x);
+  }
+  row_store<NCH>(acc, d_pano + row * H, lane);
+}
+
 }  // namespace etp
+
+#define ETP_TRAJ_NODES_CHECKS(rows_ptr, out_ptr)                                                                                        \
+  ETP_REQUIRE(rows_ptr && step_off && step_vp && view_lens && cand_count && cand_vp && gmap_id && gmap_len && out_ptr && status,        \
+              "null pointer");                                                                                                          \
+  ETP_REQUIRE(H == 256 || H == 512 || H == 768, "hidden size must be 256, 512 or 768");                                                 \
+  ETP_REQUIRE(B >= 1 && R >= 1 && V >= 1 && G >= 1, "B, R, V and G are positive");                                                      \
+  ETP_REQUIRE(Kmax >= 1 && Kmax <= 64, "Kmax lies in 1 .. 64");                                                                         \
+  ETP_REQUIRE((long)B * G <= 0x7FFFFFFFL / 4 && (long)R * V <= 0x7FFFFFFFL / 4, "B * G or R * V rows exceed the grid");                 \
+  ETP_REQUIRE(((uintptr_t)rows_ptr | (uintptr_t)out_ptr) % 16 == 0, "the feature operands must be 16-byte aligned");                    \
+  ETP_REQUIRE((uintptr_t)view_lens % 8 == 0, "view_lens must be 8-byte aligned");                                                       \
+  ETP_REQUIRE(((uintptr_t)step_off | (uintptr_t)step_vp | (uintptr_t)cand_count | (uintptr_t)cand_vp | (uintptr_t)gmap_id |             \
+               (uintptr_t)gmap_len | (uintptr_t)status) % 4 == 0, "int32 operands must be 4-byte aligned")
+
+extern "C" int etp_traj_nodes_fwd(const float* pano, const int32_t* step_off, const int32_t* step_vp, const int64_t* view_lens,
+                                  const int32_t* cand_count, const int32_t* cand_vp, const int32_t* gmap_id, const int32_t* gmap_len, int B,
+                                  int R, int V, int Kmax, int G, int H, float* gmap_img_fts, int32_t* status, etp_stream_t stream) {
+  using namespace etp;
+  ETP_TRAJ_NODES_CHECKS(pano, gmap_img_fts);
+  const dim3 grid((unsigned)(((long)B * G + 3) / 4)), block(256);
+  ETP_DISPATCH_H(H, ETP_LAUNCH((traj_nodes_fwd_kernel<NCH>), grid, block, 0, (hipStream_t)stream, pano, step_off, step_vp, view_lens,
+                               cand_count, cand_vp, gmap_id, gmap_len, B, R, V, Kmax, G, gmap_img_fts, status));
+  ETP_CHECK_LAUNCH("traj_nodes_fwd");
+  return ETP_OK;
+}
+
+extern "C" int etp_traj_nodes_bwd(const float* d_gmap_img_fts, const int32_t* step_off, const int32_t* step_vp, const int64_t* view_lens,
+                                  const int32_t* cand_count, const int32_t* cand_vp, const int32_t* gmap_id, const int32_t* gmap_len, int B,
+                                  int R, int V, int Kmax, int G, int H, float* d_pano, int32_t* status, etp_stream_t stream) {
+  using namespace etp;
+  ETP_TRAJ_NODES_CHECKS(d_gmap_img_fts, d_pano);
+  const dim3 grid((unsigned)(((long)R * V + 3) / 4)), block(256);
+  ETP_DISPATCH_H(H, ETP_LAUNCH((traj_nodes_bwd_kernel<NCH>), grid, block, 0, (hipStream_t)stream, d_gmap_img_fts, step_off, step_vp,
+                               view_lens, cand_count, cand_vp, gmap_id, gmap_len, B, R, V, Kmax, G, d_pano, status));
+  ETP_CHECK_LAUNCH("traj_nodes_bwd");
+  return ETP_OK;
+}
 
 extern "C" int etp_traj_views(const float* img_store, const float* dep_store, const int32_t* pano_row, const int32_t* cand_count,
                               const int32_t* cand_view, const float* cand_loc, const float* view_loc_tab, int R, int V, int Kmax, int P,

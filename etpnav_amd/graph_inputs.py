@@ -28,6 +28,10 @@ device tensors.
   ss_trainer_ETP.py:838-839, 864-865) in one launch and hands back the row numbers ``update`` / ``update_graph`` take; the backward of
   every later ``img_fts`` / ``gather_rows`` reaches the panorama encoder of the step that wrote a row.
 
+* ``traj_descriptors`` / ``aggregate_gmap_features(..., traj_dev=)``: the pre-training node features (``_aggregate_gmap_features``,
+  pretrain vilmodel.py:585-619) from integer tables on the device (``etp_traj_nodes_fwd`` / ``_bwd``, csrc/traj_batch.hip) instead of
+  ``pack_traj_csr``'s host-built CSR; the same bits.
+
 ``cur_heading`` is the scalar heading (radians) that the reference obtains with ``heading_from_quaternion(cur_ori)``
 (graph_utils.py:54-59); quaternion handling belongs to the simulator side and is out of scope.
 """
@@ -854,12 +858,128 @@ def pack_traj_csr(traj_vp_lens: Sequence[Sequence[int]], traj_vpids: Sequence[Se
     return (i32(ptr_f), i32(idx_f), f32(w_f)), (i32(ptr_b), i32(idx_b), f32(w_b))
 
 
-def aggregate_gmap_features(traj_embeds: torch.Tensor, traj_vp_lens, traj_vpids, traj_cand_vpids, gmap_vpids, G: int):
+TRAJ_KMAX = 64                                                # etp_traj_nodes_*: candidate slots per step (one lane per slot)
+TRAJ_ERR_COUNT_OR_LEN, TRAJ_ERR_VIEWS, TRAJ_ERR_STEPS, TRAJ_ERR_NODE = 1, 8, 16, 32     # ETP_TRAJ_ERR_* of etp_traj_nodes_fwd / _bwd
+TRAJ_TABLES = ("step_off", "step_vp", "cand_count", "cand_vp", "gmap_id", "gmap_len")
+
+
+def traj_descriptors(traj: dict, G: int, device) -> dict:
+    """The integer tables etp_traj_nodes_fwd / _bwd read (include/etpnav_hip.h), from the string lists of any trajectory batch
+    (``traj_vpids``, ``traj_cand_vpids``, ``gmap_vpids``): -> {step_off [B+1], step_vp [R], cand_count [R], cand_vp [R, Kmax], gmap_id [B, G],
+    gmap_len [B]} int32 on ``device`` plus ``Kmax``.  Ids number a sample's viewpoints in the order they first appear; -1 is [stop] and
+    padding.  One buffer (pinned when the device is a GPU), one copy.  The native loaders (pretrain_data.py) stage the same tables from
+    their cached records instead."""
+    vpids, cands, gvps = traj["traj_vpids"], traj["traj_cand_vpids"], traj["gmap_vpids"]
+    B = len(vpids)
+    steps = np.asarray([len(p) for p in vpids], dtype=np.int64)
+    R = int(steps.sum())
+    counts = np.asarray([len(c) for s in cands for c in s], dtype=np.int32)
+    if len(cands) != B or len(gvps) != B or counts.size != R or any(len(s) != len(p) for s, p in zip(cands, vpids)):
+        raise ValueError("traj_vpids, traj_cand_vpids and gmap_vpids describe different batches")
+    Kmax = max(1, int(counts.max()) if R else 0)
+    if Kmax > TRAJ_KMAX:
+        raise ValueError(f"{Kmax} candidates at one step (at most {TRAJ_KMAX})")
+    if max(len(g) for g in gvps) > G:
+        raise ValueError(f"G={G} < {max(len(g) for g in gvps)} graph entries")
+    shapes = {"step_off": (B + 1,), "step_vp": (R,), "cand_count": (R,), "cand_vp": (R, Kmax), "gmap_id": (B, G), "gmap_len": (B,)}
+    offs, total = {}, 0
+    for k in TRAJ_TABLES:
+        offs[k] = total
+        total += (int(np.prod(shapes[k])) + 3) // 4 * 4       # 16-byte pieces
+    dev = torch.device(device)
+    stage = torch.empty(total, dtype=torch.int32, pin_memory=dev.type == "cuda")
+    host = stage.numpy()
+    h = {k: host[offs[k]:offs[k] + int(np.prod(shapes[k]))].reshape(shapes[k]) for k in TRAJ_TABLES}
+    host[:] = -1
+    h["step_off"][0] = 0
+    np.cumsum(steps, out=h["step_off"][1:])
+    h["cand_count"][:] = counts
+    h["gmap_len"][:] = [len(g) for g in gvps]
+    r = 0
+    for i in range(B):
+        ids: Dict[str, int] = {}
+        num = lambda vp: ids.setdefault(vp, len(ids))
+        for t, vp in enumerate(vpids[i]):
+            h["step_vp"][r] = num(vp)
+            c = cands[i][t]
+            if c:
+                h["cand_vp"][r, :len(c)] = [num(x) for x in c]
+            r += 1
+        h["gmap_id"][i, :len(gvps[i])] = [-1 if vp is None else num(vp) for vp in gvps[i]]
+    d = stage.to(dev, non_blocking=True)
+    out = {k: d[offs[k]:offs[k] + int(np.prod(shapes[k]))].view(shapes[k]) for k in TRAJ_TABLES}
+    out["Kmax"] = Kmax
+    return out
+
+
+def traj_status_message(status: np.ndarray, n_nodes: int, G: int) -> Optional[str]:
+    """what the status words of etp_traj_nodes_fwd (the first ``n_nodes`` = B*G) and etp_traj_nodes_bwd (one per step) report, or None"""
+    status = np.asarray(status)
+    if not status.any():
+        return None
+    f, b = status[:n_nodes], status[n_nodes:]
+    rows = [f"(sample {i // G}, node {i % G}): {int(f[i])}" for i in np.nonzero(f)[0].tolist()]
+    steps = [f"step {i}: {int(b[i])}" for i in np.nonzero(b)[0].tolist()]
+    return ("etp_traj_nodes flagged (ETP_TRAJ_ERR_*: 1 cand_count outside 0 .. Kmax or gmap_len outside 1 .. G, 8 view_lens outside "
+            "1 .. V, 16 malformed step range, 32 a listed node neither visited nor named) -- forward rows " + (", ".join(rows) or "none") +
+            "; backward " + (", ".join(steps) or "none"))
+
+
+def traj_table_args(td: dict, view_lens: torch.Tensor) -> list:
+    """the seven table pointers of etp_traj_nodes_fwd / _bwd, in the entry points' order"""
+    return [ptr(td["step_off"]), ptr(td["step_vp"]), ptr(view_lens), ptr(td["cand_count"]), ptr(td["cand_vp"]), ptr(td["gmap_id"]),
+            ptr(td["gmap_len"])]
+
+
+class _TrajNodes(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pano, view_lens, td, dims, status):
+        B, R, V, G, H = dims
+        out = torch.empty(B * G, H, dtype=torch.float32, device=pano.device)
+        s = torch.cuda.current_stream(pano.device).cuda_stream
+        check(_lib.lib().etp_traj_nodes_fwd(ptr(pano), *traj_table_args(td, view_lens), B, R, V,
+                                            td["Kmax"], G, H, ptr(out), ptr(status), s), "etp_traj_nodes_fwd")
+        ctx.td, ctx.view_lens, ctx.dims, ctx.status = td, view_lens, dims, status
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        B, R, V, G, H = ctx.dims
+        d_out = d_out.float().contiguous()
+        if d_out.data_ptr() % 16:
+            d_out = d_out.clone()
+        d_pano = torch.empty(R * V, H, dtype=torch.float32, device=d_out.device)
+        s = torch.cuda.current_stream(d_out.device).cuda_stream
+        td = ctx.td
+        check(_lib.lib().etp_traj_nodes_bwd(ptr(d_out), *traj_table_args(td, ctx.view_lens), B, R,
+                                            V, td["Kmax"], G, H, ptr(d_pano), ctx.status.data_ptr() + 4 * B * G, s), "etp_traj_nodes_bwd")
+        return d_pano, None, None, None, None
+
+
+def aggregate_gmap_features(traj_embeds: torch.Tensor, traj_vp_lens, traj_vpids, traj_cand_vpids, gmap_vpids, G: int,
+                            traj_dev: Optional[dict] = None):
     """Device version of GlobalMapEncoder._aggregate_gmap_features: traj_embeds [sum T, V, H] (output of the panorama
-    encoder for every trajectory step) -> gmap_img_fts [B, G, H] incl. the zero [stop] row; differentiable."""
+    encoder for every trajectory step) -> gmap_img_fts [B, G, H] incl. the zero [stop] row; differentiable.
+    ``traj_dev`` (``traj_descriptors`` or a loader's ``TrajBatch.traj_dev``): no CSR is built, etp_traj_nodes_fwd / _bwd read the tables;
+    ``traj_vp_lens`` may then be the device tensor ``view_lens`` [sum T] int64 and the three string lists are not read.  The kernels'
+    status words land in ``traj_dev['status']`` [B*G + sum T]: ``traj_status_message`` reads them (nothing synchronises here)."""
     if traj_embeds.device.type != "cuda":
-        raise _lib.EtpError("etp_gather_sum needs an MI355X (cuda/hip device); no CPU fallback exists")
+        raise _lib.EtpError("etp_gather_sum / etp_traj_nodes_fwd need an MI355X (cuda/hip device); no CPU fallback exists")
     R, V, H = traj_embeds.shape
+    if traj_dev is not None:
+        dev, B = traj_embeds.device, int(traj_dev["gmap_len"].numel())
+        if tuple(traj_dev["gmap_id"].shape) != (B, G) or traj_dev["step_vp"].numel() != R:
+            raise ValueError(f"the descriptors hold {traj_dev['step_vp'].numel()} steps and nodes {tuple(traj_dev['gmap_id'].shape)}; "
+                             f"the call has {R} steps and G={G}")
+        if torch.is_tensor(traj_vp_lens):
+            vl = traj_vp_lens.to(dev, torch.int64).reshape(-1).contiguous()
+        else:
+            vl = torch.tensor([int(n) for s in traj_vp_lens for n in s], dtype=torch.int64).to(dev)
+        if vl.numel() != R:
+            raise ValueError(f"{vl.numel()} view lengths for {R} steps")
+        traj_dev["status"] = status = torch.zeros(B * G + R, dtype=torch.int32, device=dev)
+        out = _TrajNodes.apply(traj_embeds.float().contiguous().view(R * V, H), vl, traj_dev, (B, R, V, G, H), status)
+        return out.view(B, G, H)
     fwd, bwd = pack_traj_csr(traj_vp_lens, traj_vpids, traj_cand_vpids, gmap_vpids, V, G)
     dev = traj_embeds.device
     fwd, bwd = tuple(x.to(dev) for x in fwd), tuple(x.to(dev) for x in bwd)

@@ -21,14 +21,15 @@ from .step import N_MLM_INPUTS, _Staging, _destroy_streams, _new_stream
 
 class MlmStep(_Staging):
     def __init__(self, model: GlocalTextPathNavCMT, batch: Dict[str, torch.Tensor], dropout=None, drop_seed: int = 0,
-                 overlap: bool = True):
+                 overlap: bool = True, traj_nodes=None):
         """batch: etpnav_amd.synthetic.make_sap_batch layout + ``txt_labels`` [B,L] (-1 = not masked, else the token id).
         dropout: None, "config" (the model config's rates; no drop_env in this task) or (p_hidden, p_attn, p_head, p_env).
         overlap: the three-stream schedule of PlannerStep -- weight gradients on an `aux` stream, the panorama branch
-        (forward and backward) on `s2` beside the text branch; False = everything on the caller's stream."""
+        (forward and backward) on `s2` beside the text branch; False = everything on the caller's stream.
+        traj_nodes: as PlannerStep's (node features from the batch's descriptor tables; check_traj())."""
         if not model._engine.cconf.use_lang2visn:
             raise _lib.EtpError("the MLM task needs a model built with use_lang2visn_attn=True (pre-training config)")
-        self._stage(model, batch, N_MLM_INPUTS, dropout, drop_seed, 0.0)
+        self._stage(model, batch, N_MLM_INPUTS, dropout, drop_seed, 0.0, traj_nodes)
         # gradient accumulation (PretrainDriver): later micro-steps keep the arena (zero_grads False) and every micro-step's mean
         # loss is scaled by 1 / accumulation steps (train_r2r.py:250-252)
         self.zero_grads, self.loss_scale = True, 1.0

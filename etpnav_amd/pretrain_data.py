@@ -9,6 +9,8 @@ Replaces the reference's ``R2RTextPathData`` / ``SapDataset`` / ``MlmDataset`` /
     store rows, candidate tables, graph-map ids / step ids / masks / position features, the action label -- no feature row.
   * ``SapBatches`` / ``MlmBatches``        iterables for MetaLoader / PretrainDriver: per batch ONE pinned staging buffer with everything
     the host built, ONE host-to-device copy, then etp_traj_views and etp_traj_pair_dists (csrc/traj_batch.hip).  No synchronisation.
+    The batch is a ``TrajBatch``: the dict, plus the trajectory's integer tables on the device (``traj_dev``) from which the steps
+    compute the node features (etp_traj_nodes_fwd / _bwd) without building a CSR from the string lists.
 
 Candidate angles are pinned to float32: ``np.float32(base) + np.float32(offset)`` (dataset.py:502-503).  That is what the reference's
 expression ``view_angle[0] + v[2]`` (a float32 scalar plus a Python float) gives under numpy 2; under the reference's own numpy 1.x the
@@ -313,7 +315,13 @@ class R2RTextPathIndex:
                 glabel = gmap_vpids.index(nxt)
             if nxt in cand_vpids[-1]:
                 llabel = cand_vpids[-1].index(nxt) + 1
+        # the trajectory as graph indices (the index space of gmap_idx): what etp_traj_nodes_fwd / _bwd read instead of the names
+        kmax = max(1, max(len(c) for c in cand_vpids))
+        cand_vp = np.full((len(path), kmax), -1, dtype=np.int32)
+        for t, c in enumerate(cand_vpids):
+            cand_vp[t, :len(c)] = [g["index"][vp] for vp in c]
         rec = {
+            "step_vp": np.asarray([g["index"][vp] for vp in path], dtype=np.int32), "cand_vp": cand_vp,
             "instr_id": item["instr_id"], "scan": scan,
             "txt": np.asarray(item["instr_encoding"][:self.max_txt_len], dtype=np.int64),
             "rows": np.asarray(rows, dtype=np.int32), "tables": tables,
@@ -331,6 +339,14 @@ class R2RTextPathIndex:
 # ---- tasks.py:55-138, 271-364 ------------------------------------------------------------------------------------------------------
 def _align(n: int, a: int = 16) -> int:
     return (n + a - 1) // a * a
+
+
+class TrajBatch(dict):
+    """The batch dict of the native loaders -- keys and values as before -- with the trajectory's integer tables on the device beside it:
+    ``traj_dev`` = {step_off [B+1], step_vp [R], cand_count [R], cand_vp [R, Kmax], gmap_id [B, G], gmap_len [B]} int32 views of the
+    batch's one staging buffer, plus ``Kmax``.  PlannerStep / MlmStep compute the node features from them (etp_traj_nodes_fwd / _bwd)
+    and build no CSR from ``traj``'s string lists."""
+    traj_dev: Optional[dict] = None
 
 
 class _Batches:
@@ -372,7 +388,7 @@ class _Batches:
                                 f"(status {st[R:][st[R:] != 0].tolist()})")
 
     def assemble(self, recs: List[dict], txt: List[np.ndarray], labels: np.ndarray, txt_labels: Optional[List[np.ndarray]] = None) -> dict:
-        """records -> the batch dict of synthetic.make_sap_batch on the device: one staging buffer, one copy, two launches"""
+        """records -> the batch dict of synthetic.make_sap_batch on the device (a TrajBatch): one staging buffer, one copy, two launches"""
         idx = self.index
         B = len(recs)
         R = sum(len(r["rows"]) for r in recs)
@@ -382,7 +398,8 @@ class _Batches:
         L = max(len(t) for t in txt)
         segs = [("pano_row", np.int32, (R,)), ("cand_count", np.int32, (R,)), ("cand_view", np.int32, (R, Kmax)),
                 ("cand_loc", np.float32, (R, Kmax, 4)), ("scan_off", np.int64, (B,)), ("scan_n", np.int32, (B,)),
-                ("gmap_idx", np.int32, (B, G)), ("gmap_len", np.int32, (B,)), ("txt_ids", np.int64, (B, L)),
+                ("gmap_idx", np.int32, (B, G)), ("gmap_len", np.int32, (B,)), ("step_off", np.int32, (B + 1,)), ("step_vp", np.int32, (R,)),
+                ("cand_vp", np.int32, (R, Kmax)), ("txt_ids", np.int64, (B, L)),
                 ("txt_masks", np.bool_, (B, L)), ("gmap_step_ids", np.int64, (B, G)), ("gmap_pos_fts", np.float32, (B, G, 7)),
                 ("gmap_visited_masks", np.bool_, (B, G)), ("labels", np.int64, (B,))]
         offs, total = {}, 0
@@ -394,9 +411,13 @@ class _Batches:
         h = {name: host[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape)
              for name, dt, shape in segs}
         r0 = 0
+        h["cand_vp"][:] = -1
         for b, rec in enumerate(recs):
             n = len(rec["rows"])
             h["pano_row"][r0:r0 + n] = rec["rows"]
+            h["step_off"][b + 1] = r0 + n
+            h["step_vp"][r0:r0 + n] = rec["step_vp"]
+            h["cand_vp"][r0:r0 + n, :rec["cand_vp"].shape[1]] = rec["cand_vp"]
             for t, (view, loc) in enumerate(rec["tables"]):
                 k = len(view)
                 h["cand_count"][r0 + t] = k
@@ -446,6 +467,9 @@ class _Batches:
             for b, t in enumerate(txt_labels):
                 tl[b, :len(t)] = torch.from_numpy(t)
             out["txt_labels"] = tl
+        out = TrajBatch(out)
+        out.traj_dev = {"step_off": d["step_off"], "step_vp": d["step_vp"], "cand_count": d["cand_count"], "cand_vp": d["cand_vp"],
+                        "gmap_id": d["gmap_idx"], "gmap_len": d["gmap_len"], "Kmax": Kmax}
         return out
 
     def _order(self):

@@ -96,7 +96,8 @@ class _Staging:
     text and panorama branches, dropout state -- and the library calls both issue with the same arguments.  The two schedules
     themselves (which stream, which order) stay written out in each class."""
 
-    def _stage(self, model: GlocalTextPathNavCMT, batch, n_inputs: int, dropout, drop_seed: int, p_env: float):
+    def _stage(self, model: GlocalTextPathNavCMT, batch, n_inputs: int, dropout, drop_seed: int, p_env: float,
+               traj_nodes: Optional[bool] = None):
         self.model = model
         eng = self.eng = model._engine
         eng.require_gpu()
@@ -111,7 +112,15 @@ class _Staging:
         G = self.G = batch["gmap_step_ids"].shape[1]
         dev, H, h = eng.device, eng.cconf.hidden, eng.handle
         self.inp = {k: batch[src].to(dt).contiguous().to(dev) for k, src, dt in INPUTS[:n_inputs]}
-        self.csr_f, self.csr_b = _node_csr(batch, V, G, dev)
+        # node features of a trajectory batch straight from its integer tables (etp_traj_nodes_fwd / _bwd, csrc/traj_batch.hip): whenever
+        # the batch carries them (TrajBatch.traj_dev of the native loaders), or forced for a string-only batch; ETP_TRAJ_NODES=0 (read
+        # once, here) or traj_nodes=False keep the host-built CSR + etp_gather_sum
+        self.traj_nodes = traj_nodes is not False and os.environ.get("ETP_TRAJ_NODES", "1") != "0" and \
+            (getattr(batch, "traj_dev", None) is not None or bool(traj_nodes))
+        self.traj_dev = self.csr_f = self.csr_b = None
+        if self.traj_nodes:
+            self.traj_status = torch.zeros(B * G + Bp, dtype=torch.int32, device=dev)    # forward [B*G] node rows, backward [Bp] steps
+        self._load_nodes(batch)
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)   # API tensors are fp32 in both modes
         self.txt, self.pano, self.pmask, self.gimg = e(B, Lt, H), e(Bp, V, H), e(Bp, V, dt=torch.bool), e(B, G, H)
         self.d_txt, self.d_gimg, self.d_pano = e(B, Lt, H), e(B, G, H), e(Bp, V, H)
@@ -145,13 +154,58 @@ class _Staging:
         check(self.L.etp_pano_bwd(self.eng.handle, ptr(self.d_pano), ptr(i["rgb"]), ptr(i["dep"]), ptr(i["loc"]), ptr(i["nav"]),
                                   self.Bp, self.V, None, ptr(self.st_pano), ptr(self.ws_pano), s2), "pano_bwd")
 
+    def _load_nodes(self, batch):
+        """what the node aggregation reads for this batch: the descriptor tables, taken by reference (Kmax may differ from batch to
+        batch), or the CSR and its transpose"""
+        if not self.traj_nodes:
+            self.csr_f, self.csr_b = _node_csr(batch, self.V, self.G, self.eng.device)
+            return
+        td = getattr(batch, "traj_dev", None)
+        if td is None:
+            if "traj" not in batch:
+                raise ValueError("traj_nodes=True needs the trajectory lists (batch['traj']) or a loader's TrajBatch")
+            from .graph_inputs import traj_descriptors
+            td = traj_descriptors(batch["traj"], self.G, self.eng.device)
+        K = int(td["Kmax"])
+        want = {"step_off": (self.B + 1,), "step_vp": (self.Bp,), "cand_count": (self.Bp,), "cand_vp": (self.Bp, K),
+                "gmap_id": (self.B, self.G), "gmap_len": (self.B,)}
+        for k, shape in want.items():
+            t = td[k]
+            if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.inp["view_lens"].device:
+                raise ValueError(f"traj_dev[{k!r}] is a contiguous int32 tensor {shape} on the step's device (got {tuple(t.shape)}, {t.dtype})")
+        if not 1 <= K <= 64:
+            raise ValueError(f"traj_dev['Kmax'] = {K} lies outside 1 .. 64")
+        self.traj_dev = td
+
+    def check_traj(self) -> None:
+        """one device-to-host copy of the status words of etp_traj_nodes_fwd / _bwd; raises EtpError naming the node rows and steps
+        they flagged.  The step itself never synchronises; a step on the CSR route has nothing to check."""
+        if not self.traj_nodes:
+            return
+        from .graph_inputs import traj_status_message
+        msg = traj_status_message(self.traj_status.cpu().numpy(), self.B * self.G, self.G)
+        if msg:
+            raise _lib.EtpError(msg)
+
+    def _traj_args(self):
+        from .graph_inputs import traj_table_args
+        return traj_table_args(self.traj_dev, self.inp["view_lens"]) + [self.B, self.Bp, self.V, int(self.traj_dev["Kmax"]), self.G,
+                                                                        self.eng.cconf.hidden]
+
     def _assemble(self, s: int):
         """node features = gather-mean of the view embeddings (fp32 API tensors)"""
+        if self.traj_nodes:
+            check(self.L.etp_traj_nodes_fwd(ptr(self.pano), *self._traj_args(), ptr(self.gimg), ptr(self.traj_status), s), "node assembly")
+            return
         pf, xf, wf = self.csr_f
         check(self.L.etp_gather_sum(_lib.ETP_F32, ptr(self.pano), ptr(pf), ptr(xf), ptr(wf), ptr(self.gimg), self.B * self.G,
                                     self.eng.cconf.hidden, 0, s), "node assembly")
 
     def _assemble_bwd(self, s: int):
+        if self.traj_nodes:
+            check(self.L.etp_traj_nodes_bwd(ptr(self.d_gimg), *self._traj_args(), ptr(self.d_pano),
+                                            self.traj_status.data_ptr() + 4 * self.B * self.G, s), "node assembly bwd")
+            return
         pb, xb, wb = self.csr_b
         check(self.L.etp_gather_sum(_lib.ETP_F32, ptr(self.d_gimg), ptr(pb), ptr(xb), ptr(wb), ptr(self.d_pano), self.Bp * self.V,
                                     self.eng.cconf.hidden, 0, s), "node assembly bwd")
@@ -160,14 +214,18 @@ class _Staging:
 class PlannerStep(_Staging):
     def __init__(self, model: GlocalTextPathNavCMT, batch: Dict[str, torch.Tensor], overlap: bool = True,
                  dropout=None, drop_seed: int = 0, refresh_weights: bool = True, zero_grads: bool = True,
-                 grad_overwrite: Optional[bool] = None, share_side_streams: Optional["PlannerStep"] = None):
+                 grad_overwrite: Optional[bool] = None, share_side_streams: Optional["PlannerStep"] = None,
+                 traj_nodes: Optional[bool] = None):
         """dropout: None (eval-mode step), "config" (the model config's rates, the reference's policy.train()), or a
         tuple (p_hidden, p_attn, p_head, p_env).  refresh_weights / zero_grads = False when etpnav_amd.optim.FusedAdamW
         closes the step: its kernel already wrote the bf16 weight shadow and zeroed the gradient arena.
         grad_overwrite: weight-gradient GEMMs store instead of accumulating (Engine.scope's grad_overwrite mode) and only the
         vector/table tail of the gradient arena is zeroed per step.  Default: on when this step owns the zeroing (fresh
         gradients every step) and every weight matrix is touched exactly once per step (not the pre-training variant, whose
-        language-side x-layer weights this step does not touch)."""
+        language-side x-layer weights this step does not touch).
+        traj_nodes: None = the node features come from the batch's descriptor tables when it carries them (a loader's TrajBatch), else
+        from the host-built CSR; True forces the tables for a string-only batch['traj'] (graph_inputs.traj_descriptors); False or
+        ETP_TRAJ_NODES=0 keep the CSR.  check_traj() reads what the table route flagged."""
         self.refresh_weights, self.zero_grads = refresh_weights, zero_grads
         # frozen sub-models (vlnbert_init.py:51-54 -> vilmodel_cmt.py:422-433,675-682): with fix_lang_embedding the text encoder's
         # output is detached (LanguageEncoder.forward :431-432) -- no text backward runs and no gradient reaches `embeddings.*` /
@@ -182,7 +240,7 @@ class PlannerStep(_Staging):
             grad_overwrite = bool(zero_grads) and not model._engine.cconf.use_lang2visn and \
                 os.environ.get("ETP_GRAD_OVERWRITE", "1") != "0"
         self.grad_overwrite = bool(grad_overwrite)
-        e = self._stage(model, batch, len(INPUTS), dropout, drop_seed, model.drop_env_prob)
+        e = self._stage(model, batch, len(INPUTS), dropout, drop_seed, model.drop_env_prob, traj_nodes)
         self.loss_scale = 1.0 / self.B                         # cross_entropy(sum) / batch_size (ss_trainer_ETP.py:892)
         eng, h, (B, Lt, G) = self.eng, self.eng.handle, (self.B, self.Lt, self.G)
         self.gemb, self.logits, self.dlogits = e(B, G, eng.cconf.hidden), e(B, G), e(B, G)
@@ -239,15 +297,16 @@ class PlannerStep(_Staging):
 
     def load_batch(self, batch: Dict[str, torch.Tensor]):
         """Refill the preallocated device inputs with another batch of the SAME shapes (the stash / workspace buffers and the
-        streams are reused; only the small CSR index arrays of the node aggregation are rebuilt)."""
+        streams are reused; only the small CSR index arrays of the node aggregation are rebuilt, or, on the table route, the new
+        batch's descriptor tensors are taken by reference)."""
         if self.batch_shape_key(batch) != self.shape_key():
             raise ValueError(f"batch shapes {self.batch_shape_key(batch)} differ from this step's {self.shape_key()}")
         if self.graphs:
-            # the CSR index tensors below are re-allocated: kernel nodes of an existing graph would keep the old pointers
+            # the CSR index tensors (the descriptor tensors) below are new allocations: kernel nodes of an existing graph would keep the old pointers
             raise RuntimeError("load_batch() on a step with captured / recorded graphs: close() the graphs (or build a new step) first")
         for k, src, dt in INPUTS:
             self.inp[k].copy_(batch[src].to(dt), non_blocking=True)
-        self.csr_f, self.csr_b = _node_csr(batch, self.V, self.G, self.eng.device)
+        self._load_nodes(batch)
 
     # ------------------------------------------------------------------------------------------
     def _enqueue_pano_bwd(self, s: int):

@@ -1075,6 +1075,45 @@ int etp_traj_pair_dists(const double* dist_tab, int64_t dist_len, const int64_t*
                         const int32_t* gmap_len, int B, int G, float* gmap_pair_dists, uint8_t* gmap_masks, int32_t* status,
                         etp_stream_t stream);
 
+/* Trajectory node features straight from a batch's integer tables (csrc/traj_batch.hip): GlobalMapEncoder._aggregate_gmap_features
+ * (pretrain_src/pretrain_src/model/vilmodel.py:585-619) and its backward, with the results of etp_gather_sum over
+ * graph_inputs.pack_traj_csr's arrays, bit for bit, and no CSR.  One launch each, one wavefront per output row.
+ *   pano [R*V, H] fp32: the panorama encoder's output for the R trajectory steps of B samples; sample b owns the steps
+ *   step_off[b] .. step_off[b+1]-1 (step_off [B+1] int32).  Per step t: step_vp [R] int32 the viewpoint's id, view_lens [R] int64 its
+ *   valid views n_t, cand_count [R] int32 and cand_vp [R, Kmax] int32 the ids its candidate slots name.  gmap_id [B, G] int32 the ids of
+ *   the sample's nodes, gmap_len [B] int32 how many are listed.  An id is any int32 >= 0, distinct per viewpoint within a sample; -1 is
+ *   the [stop] entry and padding; the ids of gmap_id[b, 1 .. len-1] are distinct.
+ * etp_traj_nodes_fwd, node row (b, g) of gmap_img_fts [B*G, H]:
+ *   g = 0 or g >= gmap_len[b]: exact zeros.
+ *   the id equals step_vp of a step of sample b: with t the LAST such step, sum over the views j < n_t ascending of w * pano[t*V + j],
+ *     w = (float)(1.0 / (double)n_t) (a later visit overwrites an earlier one, :603-607).
+ *   otherwise every candidate slot (t, j), j < cand_count[t], whose cand_vp equals the id counts; the slots with j < n_t contribute
+ *     w * pano[t*V + j] in the order t ascending, then j ascending, w = (float)(1.0 / (double)count): a slot beyond the valid views is a
+ *     zero row of the reference (embeds * vp_masks, :599-600) that still counts in the mean.
+ *   a listed node that is neither visited nor named: ETP_TRAJ_ERR_NODE, the row keeps what it held.
+ * etp_traj_nodes_bwd, panorama row (t, j) of d_pano [R*V, H], t a step of sample b; at most two nodes read the row:
+ *   (A) j < n_t, t is the last visit of step_vp[t] and that id is listed in gmap_id[b]: weight 1/n_t;
+ *   (B) j < cand_count[t], j < n_t, cand_vp[t, j] is visited nowhere in the sample and is listed: weight 1/count;
+ *   added in ascending node index; every other row is exact zeros.
+ * Both accumulate acc = fma(w, x, acc) per element from +0 in the order stated, which is etp_gather_sum's operation.
+ * status: forward [B*G] int32 per node row, backward [R] int32 per step (written by the wave of view 0) = 0, or the OR of
+ *   ETP_TRAJ_ERR_STEPS (the sample's step range is not 0 <= step_off[b] < step_off[b+1] <= R; backward: also a step no sample owns),
+ *   ETP_TRAJ_ERR_COUNT (a cand_count of the sample outside 0 .. Kmax), ETP_TRAJ_ERR_VIEWS (a view_lens of the sample outside 1 .. V),
+ *   ETP_TRAJ_ERR_LEN (gmap_len[b] outside 1 .. G; it shares the value of ETP_TRAJ_ERR_COUNT, as in the two calls above) and, forward
+ *   only, ETP_TRAJ_ERR_NODE.  A flagged wave writes its status word and leaves its row alone; nothing is indexed by an unchecked value.
+ * ETP_ERR_INVALID before anything is launched: a NULL operand, H outside {256, 512, 768}, B, R, V or G < 1, Kmax outside 1 .. 64,
+ *   B*G or R*V rows beyond the grid, pano / gmap_img_fts / d_gmap_img_fts / d_pano not 16-byte, view_lens not 8-byte or an int32 operand
+ *   not 4-byte aligned.
+ * Plain vector stores, no atomics, no LDS, no scratch; a second run gives the same bits. */
+#define ETP_TRAJ_ERR_STEPS 16
+#define ETP_TRAJ_ERR_NODE 32
+int etp_traj_nodes_fwd(const float* pano, const int32_t* step_off, const int32_t* step_vp, const int64_t* view_lens,
+                       const int32_t* cand_count, const int32_t* cand_vp, const int32_t* gmap_id, const int32_t* gmap_len, int B, int R,
+                       int V, int Kmax, int G, int H, float* gmap_img_fts, int32_t* status, etp_stream_t stream);
+int etp_traj_nodes_bwd(const float* d_gmap_img_fts, const int32_t* step_off, const int32_t* step_vp, const int64_t* view_lens,
+                       const int32_t* cand_count, const int32_t* cand_vp, const int32_t* gmap_id, const int32_t* gmap_len, int B, int R,
+                       int V, int Kmax, int G, int H, float* d_pano, int32_t* status, etp_stream_t stream);
+
 /* Pre-training MLM task for a planner created with cfg.use_lang2visn = 1:
  * GlocalTextPathCMT.forward_mlm (pretrain vilmodel.py:708-754): the text (output of etp_txt_fwd) attends to the graph-node
  * inputs gmap_img_fts + step + position embeddings through forward_lang2visn of every x-layer (:400-411), then
