@@ -637,6 +637,18 @@ int etp_vocab_ce(int dtype, const float* logits, const int64_t* labels, float* l
   ETP_REQUIRE(Nm > 0 && V > 0 && ldv >= V, "Nm > 0, V > 0 and ldv >= V required");
   return vocab_ce(dtype, logits, labels, loss, dlogits, Nm, V, ldv, scale, (hipStream_t)s);
 }
+int etp_vocab_eval(const float* logits, const int64_t* labels, int Nm, int V, int ldv, float* row_nll, int32_t* row_pred,
+                   etp_stream_t s) {
+  return vocab_eval(logits, labels, Nm, V, ldv, row_nll, row_pred, (hipStream_t)s);
+}
+int etp_sap_eval(const float* logits, const int64_t* labels, int B, int G, int64_t ignore_index, float* row_nll, int32_t* row_pred,
+                 etp_stream_t s) {
+  return sap_eval(logits, labels, B, G, (long)ignore_index, row_nll, row_pred, (hipStream_t)s);
+}
+int etp_eval_accum(const float* row_nll, const int32_t* row_pred, const int64_t* labels, int n, int64_t ignore_index,
+                   etp_eval_record* acc, etp_stream_t s) {
+  return eval_accum(row_nll, row_pred, labels, n, (long)ignore_index, acc, (hipStream_t)s);
+}
 int etp_gelu_bwd(int dtype, void* d, const void* z, int64_t n, etp_stream_t s) {
   ETP_REQUIRE(dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
   ETP_REQUIRE(d && z && n >= 0, "null pointer / negative count");

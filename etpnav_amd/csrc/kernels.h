@@ -66,6 +66,12 @@ int copy_f32(const float* src, float* dst, long n, hipStream_t st);
 int vocab_ce(int dtype, const float* logits, const int64_t* labels, float* loss, void* dl, int Nm, int V, int ldv, float scale,
              hipStream_t st);
 int gelu_bwd_inplace(int dtype, void* d, const void* z, long n, hipStream_t st);
+// eval_tail.hip: the validation tails (per-row nll and arg-max) and the device-resident counters
+int vocab_eval(const float* logits, const int64_t* labels, int Nm, int V, int ldv, float* row_nll, int32_t* row_pred, hipStream_t st);
+int sap_eval(const float* logits, const int64_t* labels, int B, int G, long ignore_index, float* row_nll, int32_t* row_pred,
+             hipStream_t st);
+int eval_accum(const float* row_nll, const int32_t* row_pred, const int64_t* labels, int n, long ignore_index, etp_eval_record* acc,
+               hipStream_t st);
 int zero_f32(float* dst, long n, hipStream_t st);
 int repeat_block(const void* src, void* dst, long bytes, int T, hipStream_t st);            // dst[t][.] = src[.], t < T
 int sum_steps(int dtype, const void* src, void* dst, long n, int steps, hipStream_t st);   // dst[i] = sum_t src[t][i], fp32 accumulation

@@ -1664,6 +1664,7 @@ struct MlmStash {
   void* langT; Act nodes; float* st0;
   std::vector<XStash> layers;
   void *wordT, *hm, *tz, *tg, *hn, *dl; float* stn; float* logits;
+  size_t logits_off;      // where `logits` starts in the plan (etp_mlm_stash_logits)
 };
 MlmStash plan_mlm(const etp_planner* pl, Bump& b, int Bn, int L, int G, int Nm) {
   const etp_config& c = pl->cfg;
@@ -1690,6 +1691,7 @@ MlmStash plan_mlm(const etp_planner* pl, Bump& b, int Bn, int L, int G, int Nm) 
   s.hn = b.take((size_t)Nm * H * es);
   s.stn = (float*)b.take((size_t)Nm * 2 * sizeof(float));
   s.dl = b.take((size_t)Nm * ldv * es);
+  s.logits_off = b.off;
   s.logits = (float*)b.take((size_t)Nm * ldv * 4);
   return s;
 }
@@ -1713,32 +1715,12 @@ MlmWs plan_mlm_ws(const etp_planner* pl, Bump& b, int Bn, int L, int G, int Nm) 
   }
   return w;
 }
-}  // namespace
-
-extern "C" {
-int64_t etp_mlm_stash_bytes(const etp_planner* p, int B, int L, int G, int Nm) {
-  if (!p || !p->cfg.use_lang2visn) return 0;
-  Bump b(nullptr);
-  plan_mlm(p, b, B, L, G, Nm);
-  return (int64_t)b.off + 256;
-}
-int64_t etp_mlm_ws_bytes(const etp_planner* p, int B, int L, int G, int Nm) {
-  if (!p || !p->cfg.use_lang2visn) return 0;
-  Bump b(nullptr);
-  plan_mlm_ws(p, b, B, L, G, Nm);
-  return (int64_t)b.off + 256;
-}
-
-int etp_mlm_fwd(etp_planner* p, const float* txt, const uint8_t* txt_mask, const int64_t* step_ids, const float* img,
-                const float* pos, const uint8_t* gmask, const int32_t* sel_ptr, const int32_t* sel_idx, const float* sel_w,
-                const int64_t* labels, int B, int L, int G, int Nm, float scale, float* loss, void* stash, etp_stream_t stream) {
-  ETP_REQUIRE(p && p->P && p->cfg.use_lang2visn, "planner was not built with use_lang2visn (pre-training variant)");
-  ETP_REQUIRE(txt && txt_mask && step_ids && img && pos && gmask && sel_ptr && sel_idx && sel_w && labels && loss && stash &&
-                  B > 0 && L > 0 && G > 0 && Nm > 0,
-              "bad arguments");
-  Ctx c = make_ctx(p, stream);
-  Bump b(stash);
-  MlmStash s = plan_mlm(p, b, B, L, G, Nm);
+// The forward both MLM entry points share, up to the fp32 logits [Nm, round_up(vocab, 8)] in the stash: etp_mlm_fwd (training: the
+// cross-entropy with its gradient follows) and etp_mlm_eval (validation: per-row nll / arg-max follow).  One body, so the two cannot
+// drift.
+static int mlm_logits_fwd(etp_planner* p, Ctx& c, MlmStash& s, const float* txt, const uint8_t* txt_mask, const int64_t* step_ids,
+                          const float* img, const float* pos, const uint8_t* gmask, const int32_t* sel_ptr, const int32_t* sel_idx,
+                          const float* sel_w, int B, int L, int G, int Nm) {
   const etp_config& cf = p->cfg;
   const int H = c.H, Mt = B * L, Mg = B * G;
   const CrossDims xd{B, L, G, gmask, 0};
@@ -1773,7 +1755,62 @@ int etp_mlm_fwd(etp_planner* p, const float* txt, const uint8_t* txt_mask, const
     g.M = Nm; g.N = cf.vocab; g.K = H; g.bias = p->pf(p->mlm_vb);
     ETP_TRY(launch_gemm(c.dt, ETP_F32, 0, 0, g, 1, c.st));
   }
-  return vocab_ce(c.dt, s.logits, labels, loss, s.dl, Nm, cf.vocab, (int)ldv, scale, c.st);
+  return ETP_OK;
+}
+}  // namespace
+
+extern "C" {
+int64_t etp_mlm_stash_bytes(const etp_planner* p, int B, int L, int G, int Nm) {
+  if (!p || !p->cfg.use_lang2visn) return 0;
+  Bump b(nullptr);
+  plan_mlm(p, b, B, L, G, Nm);
+  return (int64_t)b.off + 256;
+}
+int64_t etp_mlm_ws_bytes(const etp_planner* p, int B, int L, int G, int Nm) {
+  if (!p || !p->cfg.use_lang2visn) return 0;
+  Bump b(nullptr);
+  plan_mlm_ws(p, b, B, L, G, Nm);
+  return (int64_t)b.off + 256;
+}
+
+int etp_mlm_fwd(etp_planner* p, const float* txt, const uint8_t* txt_mask, const int64_t* step_ids, const float* img,
+                const float* pos, const uint8_t* gmask, const int32_t* sel_ptr, const int32_t* sel_idx, const float* sel_w,
+                const int64_t* labels, int B, int L, int G, int Nm, float scale, float* loss, void* stash, etp_stream_t stream) {
+  ETP_REQUIRE(p && p->P && p->cfg.use_lang2visn, "planner was not built with use_lang2visn (pre-training variant)");
+  ETP_REQUIRE(txt && txt_mask && step_ids && img && pos && gmask && sel_ptr && sel_idx && sel_w && labels && loss && stash &&
+                  B > 0 && L > 0 && G > 0 && Nm > 0,
+              "bad arguments");
+  Ctx c = make_ctx(p, stream);
+  Bump b(stash);
+  MlmStash s = plan_mlm(p, b, B, L, G, Nm);
+  ETP_TRY(mlm_logits_fwd(p, c, s, txt, txt_mask, step_ids, img, pos, gmask, sel_ptr, sel_idx, sel_w, B, L, G, Nm));
+  return vocab_ce(c.dt, s.logits, labels, loss, s.dl, Nm, p->cfg.vocab, (int)round_up(p->cfg.vocab, 8), scale, c.st);
+}
+
+int etp_mlm_eval(etp_planner* p, const float* txt, const uint8_t* txt_mask, const int64_t* step_ids, const float* img,
+                 const float* pos, const uint8_t* gmask, const int32_t* sel_ptr, const int32_t* sel_idx, const float* sel_w,
+                 const int64_t* labels, int B, int L, int G, int Nm, void* stash, float* row_nll, int32_t* row_pred,
+                 etp_eval_record* acc, etp_stream_t stream) {
+  ETP_REQUIRE(p && p->P && p->cfg.use_lang2visn, "planner was not built with use_lang2visn (pre-training variant)");
+  ETP_REQUIRE(txt && txt_mask && step_ids && img && pos && gmask && sel_ptr && sel_idx && sel_w && labels && stash && row_nll &&
+                  row_pred && acc && B > 0 && L > 0 && G > 0 && Nm > 0,
+              "bad arguments");
+  ETP_REQUIRE((uintptr_t)acc % 8 == 0, "the record must be 8-byte aligned");
+  Ctx c = make_ctx(p, stream);
+  Bump b(stash);
+  MlmStash s = plan_mlm(p, b, B, L, G, Nm);
+  ETP_TRY(mlm_logits_fwd(p, c, s, txt, txt_mask, step_ids, img, pos, gmask, sel_ptr, sel_idx, sel_w, B, L, G, Nm));
+  ETP_TRY(vocab_eval(s.logits, labels, Nm, p->cfg.vocab, (int)round_up(p->cfg.vocab, 8), row_nll, row_pred, c.st));
+  return eval_accum(row_nll, row_pred, labels, Nm, -1, acc, c.st);
+}
+
+int etp_mlm_stash_logits(const etp_planner* p, int B, int L, int G, int Nm, int64_t* byte_offset, int64_t* ldv) {
+  ETP_REQUIRE(p && p->cfg.use_lang2visn, "planner was not built with use_lang2visn (pre-training variant)");
+  ETP_REQUIRE(byte_offset && ldv && B > 0 && L > 0 && G > 0 && Nm > 0, "bad arguments");
+  Bump b(nullptr);
+  *byte_offset = (int64_t)plan_mlm(p, b, B, L, G, Nm).logits_off;
+  *ldv = round_up(p->cfg.vocab, 8);
+  return ETP_OK;
 }
 
 int etp_mlm_bwd(etp_planner* p, const float* txt, const uint8_t* txt_mask, const int64_t* step_ids, const float* pos,

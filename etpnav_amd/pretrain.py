@@ -9,7 +9,9 @@ pre-training config, run_pt/r2r_model_config_dep.json).  The SAP task of the sam
 """
 from __future__ import annotations
 
-from typing import List, Dict
+import ctypes
+import time
+from typing import List, Dict, Optional
 
 import torch
 
@@ -50,6 +52,7 @@ class MlmStep(_Staging):
         self.st_mlm = eng.buf(self.L.etp_mlm_stash_bytes(eng.handle, B, Lt, G, Nm))
         self.ws_mlm = eng.buf(self.L.etp_mlm_ws_bytes(eng.handle, B, Lt, G, Nm))
         self.aux, self.s2 = (_new_stream(self.L), _new_stream(self.L)) if overlap else (None, None)
+        self.row_nll = self.row_pred = None    # run_eval's per-row outputs, allocated at its first call
 
     @staticmethod
     def batch_shape_key(batch):
@@ -73,7 +76,30 @@ class MlmStep(_Staging):
         finally:   # the aux stream is this step's own: off the handle on every exit
             self.eng.release_aux()
 
-    def _enqueue(self, s: int, backward: bool):
+    def run_eval(self, counters):
+        """validate_mlm's loop body (train_r2r.py:362-368) on this batch: the schedule of ``run_eager(backward=False)`` with
+        etp_mlm_eval in place of etp_mlm_fwd -- per-row nll / arg-max into ``row_nll`` / ``row_pred``, their sums added to
+        `counters` (etpnav_amd.validate.EvalCounters) on the device.  No loss, no dlogits, no host read."""
+        if self.row_nll is None:
+            self.row_nll = torch.empty(self.Nm, dtype=torch.float32, device=self.eng.device)
+            self.row_pred = torch.empty(self.Nm, dtype=torch.int32, device=self.eng.device)
+        self.step_no += 1
+        try:
+            with self.eng.scope(aux=self.aux, aux2=None, lazy=0, drop=self._drop_state()):
+                self._enqueue(self.eng.stream(), False, counters)
+        finally:
+            self.eng.release_aux()
+
+    def scores(self) -> torch.Tensor:
+        """model(batch, task='mlm', compute_loss=False) (train_r2r.py:362): a view [Nm, vocab] of the fp32 logits the last
+        run_eager / run_eval left in the stash."""
+        off, ldv = ctypes.c_int64(), ctypes.c_int64()
+        check(self.L.etp_mlm_stash_logits(self.eng.handle, self.B, self.Lt, self.G, self.Nm, ctypes.byref(off), ctypes.byref(ldv)),
+              "mlm_stash_logits")
+        n = self.Nm * ldv.value * 4
+        return self.st_mlm[off.value:off.value + n].view(torch.float32).view(self.Nm, ldv.value)[:, :self.eng.cconf.vocab]
+
+    def _enqueue(self, s: int, backward: bool, counters=None):
         L, h, i = self.L, self.eng.handle, self.inp
         s2 = self.s2 if self.s2 is not None else s
         B, Lt, G, Nm = self.B, self.Lt, self.G, self.Nm
@@ -89,6 +115,11 @@ class MlmStep(_Staging):
         self._pano_fwd(s2)
         check(L.etp_stream_after(s2, s), "join")
         self._assemble(s)
+        if counters is not None:
+            check(L.etp_mlm_eval(h, ptr(self.txt), ptr(i["txt_masks"]), ptr(i["step_ids"]), ptr(self.gimg), ptr(i["pos"]),
+                                 ptr(i["gmask"]), ptr(self.sel[0]), ptr(self.sel[1]), ptr(self.sel[2]), ptr(self.labels), B, Lt, G,
+                                 Nm, ptr(self.st_mlm), ptr(self.row_nll), ptr(self.row_pred), counters.ptr(), s), "mlm_eval")
+            return
         check(L.etp_mlm_fwd(h, ptr(self.txt), ptr(i["txt_masks"]), ptr(i["step_ids"]), ptr(self.gimg), ptr(i["pos"]),
                             ptr(i["gmask"]), ptr(self.sel[0]), ptr(self.sel[1]), ptr(self.sel[2]), ptr(self.labels), B, Lt, G,
                             Nm, self.loss_scale / Nm, ptr(self.loss), ptr(self.st_mlm), s), "mlm_fwd")
@@ -209,6 +240,7 @@ class PretrainDriver:
         self.global_step = 0
         self.distributed = distributed
         self._sap = {}                      # shape key -> PlannerStep
+        self._sap_eval = {}                 # shape key -> PlannerStep of validate(): no dropout, apart from the training cache
         self._max = max_cached_steps
         self.reducers = {}
         if distributed:
@@ -217,6 +249,7 @@ class PretrainDriver:
                 self.reducers[task] = dp.GradReducer(model.flat_grads, ranges, sparse_rows=sparse)
         self.task_losses = {}
         self.lr_history = []
+        self.val_logs = []                  # (global_step, dict) of every validation point of run()
 
     def _sap_step(self, batch):
         from .step import PlannerStep
@@ -283,15 +316,79 @@ class PretrainDriver:
             st.close()
         return loss
 
-    def run(self, num_steps: int):
+    def _sap_eval_step(self, batch):
+        from .step import PlannerStep
+        key = PlannerStep.batch_shape_key(batch)
+        st = self._sap_eval.get(key)
+        if st is None:
+            if len(self._sap_eval) >= self._max:
+                self._sap_eval.pop(next(iter(self._sap_eval))).close()
+            st = self._sap_eval[key] = PlannerStep(self.model, batch, dropout=None, zero_grads=False, grad_overwrite=False)
+        else:
+            st.load_batch(batch)
+        return st
+
+    def validate(self, val_loaders: Dict, setname: str = "") -> Dict[str, float]:
+        """validate() of train_r2r.py:335-444 (model.eval(): no dropout): for every task of `val_loaders` ({task: batches}) one
+        pass over its batches with the loss sum, the correct rows and the row count kept on the device, read once per task
+        and summed over the ranks.  -> {'val{setname}_{task}_loss' / '_acc' / '_tok_per_s'} for an MLM task,
+        {'..._gloss' / '_gacc' / '_tok_per_s'} for a SAP task.  Parameters, gradients, optimizer state and the training step
+        cache are left as they are."""
+        from .validate import EvalCounters, sap_eval, sum_over_ranks
+        out = {}
+        for name in val_loaders:
+            if name.split("_")[0] not in ("mlm", "sap"):
+                raise ValueError(f"unknown task {name!r}: this fork validates 'mlm' and 'sap' (train_r2r.py:339-346)")
+        counters = EvalCounters(self.model._engine.device)
+        for name, loader in val_loaders.items():
+            task = name.split("_")[0]
+            counters.reset()
+            t0 = time.time()
+            for batch in loader:
+                if task == "sap":
+                    st = self._sap_eval_step(batch)
+                    st.run_eager(backward=False)
+                    sap_eval(st, counters)
+                else:
+                    st = MlmStep(self.model, batch, dropout=None)
+                    st.run_eval(counters)
+                    torch.cuda.current_stream().synchronize()      # the per-batch MLM step object is released, as in train_step
+                    st.close()
+            loss_sum, n_correct, n_rows = sum_over_ranks(counters.read())
+            dt = time.time() - t0
+            keys = ("loss", "acc") if task == "mlm" else ("gloss", "gacc")
+            log = {keys[0]: loss_sum / n_rows, keys[1]: n_correct / n_rows, "tok_per_s": n_rows / dt}
+            out.update({f"val{setname}_{name}_{k}": v for k, v in log.items()})
+        return out
+
+    def run(self, num_steps: int, valid_steps: Optional[int] = None, val_loaders=None, val2_loaders=None, on_checkpoint=None):
+        """num_steps optimizer steps.  With valid_steps, the validation points of train_r2r.py:319-332: after every valid_steps-th
+        optimizer step, and once more at the end when the last step was not such a multiple, validate(val_loaders, '_seen'), then
+        validate(val2_loaders, '_unseen'), then on_checkpoint(global_step) where the reference saves the model.  The dicts are
+        kept in ``self.val_logs`` as (global_step, dict)."""
         it = iter(self.meta)
         out = []
         for _ in range(num_steps * self.accum_steps):       # num_steps OPTIMIZER steps
             name, batch = next(it)
             out.append((name, self.train_step(name, batch)))
+            if valid_steps and self._micro == 0 and self.global_step % valid_steps == 0:
+                self._validation_point(val_loaders, val2_loaders, on_checkpoint)
+        if valid_steps and num_steps > 0 and self.global_step % valid_steps != 0:
+            self._validation_point(val_loaders, val2_loaders, on_checkpoint)
         return out
 
+    def _validation_point(self, val_loaders, val2_loaders, on_checkpoint):
+        log = {}
+        if val_loaders is not None:
+            log.update(self.validate(val_loaders, setname="_seen"))
+        if val2_loaders is not None:
+            log.update(self.validate(val2_loaders, setname="_unseen"))
+        self.val_logs.append((self.global_step, log))
+        if on_checkpoint is not None:
+            on_checkpoint(self.global_step)
+
     def close(self):
-        for st in self._sap.values():
+        for st in list(self._sap.values()) + list(self._sap_eval.values()):
             st.close()
         self._sap.clear()
+        self._sap_eval.clear()

@@ -1134,6 +1134,48 @@ int etp_mlm_bwd(etp_planner* p, const float* txt_embeds, const uint8_t* txt_mask
                 void* ws, etp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Pre-training validation (pretrain_src/pretrain_src/train_r2r.py:335-444): the loss / arg-max tails of validate_mlm and
+ * validate_sap and counters that stay on the device across batches (csrc/eval_tail.hip).  No atomics, every summation order is
+ * fixed: a second run on the same inputs gives the same bits.  Tie and special-value semantics are torch's on the CPU: ties of the
+ * maximum go to the lowest column, a label on a -inf logit gives nll = +inf, a row of only -inf gives pred 0 and a NaN nll.
+ * PRECONDITION: no NaN in the logits.  Every entry refuses (ETP_ERR_INVALID, nothing launched) NULL pointers and counts < 1.
+ * ---------------------------------------------------------------------------------------------------- */
+/* what validate_mlm / validate_sap keep on the host (train_r2r.py:357-359, :418-420), on the device; 8-byte aligned */
+typedef struct etp_eval_record {
+  double loss_sum;     /* val_loss / val_gloss before the division */
+  int64_t n_correct;   /* rows with label != ignore_index and pred == label */
+  int64_t n_rows;      /* n_word / n_data: every row handed in, ignored ones included (labels.numel(), len(labels)) */
+  int64_t n_counted;   /* rows whose label is not ignore_index */
+} etp_eval_record;
+/* F.cross_entropy(scores, labels, reduction='sum') and scores.max(dim=-1)[1] of train_r2r.py:365-367, per row: logits fp32 [Nm, ldv],
+ * columns >= V are padding and are never read; labels [Nm] (there is no ignore_index: the caller gathers the masked tokens).  Writes
+ * row_nll[r] = lse_r - logits[r, y_r] (fp32; NaN where y_r is outside [0, V), which is never used as an index) and row_pred[r]
+ * (int32).  One workgroup per row; the row sum runs in etp_vocab_ce's order.  Refused besides: V < 1, ldv < V. */
+int etp_vocab_eval(const float* logits, const int64_t* labels, int Nm, int V, int ldv, float* row_nll, int32_t* row_pred,
+                   etp_stream_t stream);
+/* F.cross_entropy(global_logits, labels, reduction='sum') and torch.argmax(global_logits, 1) of train_r2r.py:424-427, per row: logits
+ * fp32 [B, G] with -inf entries; a row whose label is ignore_index writes nll = 0 (its pred is still the arg-max); any other label
+ * outside [0, G) writes NaN.  One wavefront per row; max / sum / lse in etp_sap_ce's order. */
+int etp_sap_eval(const float* logits, const int64_t* labels, int B, int G, int64_t ignore_index, float* row_nll, int32_t* row_pred,
+                 etp_stream_t stream);
+/* val_loss += loss.item(); n_correct += (pred == labels).sum().item(); n_word += labels.numel() of train_r2r.py:366-368 (:424-430 for
+ * SAP) without the .item(): *acc += the n rows, in double, in an order fixed by the row index (one workgroup).  Rows whose label is
+ * ignore_index add to n_rows only.  acc is device memory, 8-byte aligned, and is read and written by this launch alone. */
+int etp_eval_accum(const float* row_nll, const int32_t* row_pred, const int64_t* labels, int n, int64_t ignore_index,
+                   etp_eval_record* acc, etp_stream_t stream);
+/* model(batch, task='mlm', compute_loss=False) of train_r2r.py:362 followed by the two launches above: etp_mlm_fwd's forward up to
+ * the logits (the same code, the same stash plan), then etp_vocab_eval and etp_eval_accum (ignore_index -1, which a gathered label
+ * never is).  Writes no dlogits and no loss.  row_nll [Nm] fp32, row_pred [Nm] int32.  Refused besides: a planner without
+ * use_lang2visn, acc not 8-byte aligned. */
+int etp_mlm_eval(etp_planner* p, const float* txt_embeds, const uint8_t* txt_masks, const int64_t* gmap_step_ids,
+                 const float* gmap_img_fts, const float* gmap_pos_fts, const uint8_t* gmap_masks, const int32_t* sel_ptr,
+                 const int32_t* sel_idx, const float* sel_w, const int64_t* labels, int B, int L, int G, int Nm, void* stash,
+                 float* row_nll, int32_t* row_pred, etp_eval_record* acc, etp_stream_t stream);
+/* Host only: where etp_mlm_fwd / etp_mlm_eval put the fp32 logits [Nm, *ldv] inside a stash of etp_mlm_stash_bytes -- the `scores`
+ * of train_r2r.py:362 are its columns [0, vocab). */
+int etp_mlm_stash_logits(const etp_planner* p, int B, int L, int G, int Nm, int64_t* byte_offset, int64_t* ldv);
+
+/* ------------------------------------------------------------------------------------------------------
  * hipGraph helpers (launch-bound inner loops are captured once and replayed) and timing.
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct etp_graph etp_graph;
