@@ -335,7 +335,79 @@ __global__ __launch_bounds__(256) void traj_nodes_bwd_kernel(const float* __rest
   row_store<NCH>(acc, d_pano + row * H, lane);
 }
 
+// ---- the MLM task's masked-row selection: _compute_masked_hidden and the label gather (pretrain_cmt.py:141-163) ------------------------
+// What MlmStep built on the host per batch (torch.nonzero, cumsum with a leading 0, the label gather), in one launch of ONE workgroup
+// of four waves that walks the n labels in chunks of 256.  In the file's idiom every wave derives everything it needs for itself:
+// each wave loads the whole chunk (four coalesced loads, the same lines for all four waves), takes the four ballots and so knows the
+// selected count of the sub-chunks below its own and of the whole chunk -- no LDS, no barrier, no atomics; the running count is a
+// wave-uniform value every wave carries alike.  Wave w then writes sub-chunk w: ptr_t[i] = the selected entries below i, and for a
+// selected entry rows[j] = i, labels[j] = the label, j that same count.  Whatever txt_labels holds, nothing leaves its range: j is
+// written only below n_expected (<= cap, checked on the host), ptr_t is clamped to n_expected, a label is clamped into 0 .. vocab-1,
+// and the entries count .. n_expected-1 of a short selection are filled with row 0 / label 0.
+__global__ __launch_bounds__(256) void mlm_select_kernel(const int32_t* __restrict__ txt_labels, int n, int vocab, int n_expected,
+                                                         int32_t* __restrict__ rows, int32_t* __restrict__ ptr_t,
+                                                         int64_t* __restrict__ labels, int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long lower = (1ull << lane) - 1;
+  int run = 0, bad = 0;
+  for (int base = 0; base < n; base += 256) {
+    int mine = -1, below = 0, all = 0;
+    unsigned long long mm = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = base + q * 64 + lane;
+      const int v = i < n ? txt_labels[i] : -1;
+      const unsigned long long m = __ballot(v != -1);
+      bad |= (v < -1 || v >= vocab);
+      const int c = __popcll(m);
+      below += q < w ? c : 0;
+      all += c;
+      if (q == w) {
+        mine = v;
+        mm = m;
+      }
+    }
+    const int i = base + w * 64 + lane;
+    const int j = run + below + __popcll(mm & lower);
+    if (i < n) {
+      ptr_t[i] = j < n_expected ? j : n_expected;
+      if (mine != -1 && j < n_expected) {
+        rows[j] = i;
+        labels[j] = mine < 0 ? 0 : (mine >= vocab ? vocab - 1 : mine);
+      }
+    }
+    run += all;
+  }
+  for (int j = run + (int)threadIdx.x; j < n_expected; j += 256) {   // a short selection: in-range filler behind it
+    rows[j] = 0;
+    labels[j] = 0;
+  }
+  if (w == 0) {
+    const int err = (run != n_expected ? ETP_MLM_ERR_COUNT : 0) | (__any(bad) ? ETP_MLM_ERR_LABEL : 0);
+    if (lane == 0) {
+      ptr_t[n] = run < n_expected ? run : n_expected;
+      status[0] = err;
+      status[1] = run;
+    }
+  }
+}
+
 }  // namespace etp
+
+extern "C" int etp_mlm_select(const int32_t* txt_labels, int n, int vocab, int n_expected, int cap, int32_t* rows, int32_t* ptr_t,
+                              int64_t* labels, int32_t* status, etp_stream_t stream) {
+  using namespace etp;
+  ETP_REQUIRE(txt_labels && rows && ptr_t && labels && status, "null pointer");
+  ETP_REQUIRE(n >= 1 && n <= (1 << 20) && vocab >= 1, "n lies in 1 .. 2^20 and vocab is positive");
+  ETP_REQUIRE(n_expected >= 0 && n_expected <= cap, "n_expected lies in 0 .. cap");
+  ETP_REQUIRE(((uintptr_t)txt_labels | (uintptr_t)rows | (uintptr_t)ptr_t | (uintptr_t)status) % 4 == 0,
+              "int32 operands must be 4-byte aligned");
+  ETP_REQUIRE((uintptr_t)labels % 8 == 0, "labels must be 8-byte aligned");
+  ETP_LAUNCH(mlm_select_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, txt_labels, n, vocab, n_expected, rows, ptr_t, labels,
+             status);
+  ETP_CHECK_LAUNCH("mlm_select");
+  return ETP_OK;
+}
 
 #define ETP_TRAJ_NODES_CHECKS(rows_ptr, out_ptr)                                                                                        \
   ETP_REQUIRE(rows_ptr && step_off && step_vp && view_lens && cand_count && cand_vp && gmap_id && gmap_len && out_ptr && status,        \

@@ -10,6 +10,7 @@ pre-training config, run_pt/r2r_model_config_dep.json).  The SAP task of the sam
 from __future__ import annotations
 
 import ctypes
+import os
 import time
 from typing import List, Dict, Optional
 
@@ -18,41 +19,133 @@ import torch
 from . import _lib
 from ._lib import check, ptr
 from .planner import GlocalTextPathNavCMT
-from .step import N_MLM_INPUTS, _Staging, _destroy_streams, _new_stream
+from .step import INPUTS, N_MLM_INPUTS, _Staging, _destroy_streams, _new_stream
+
+MLM_ERR_COUNT, MLM_ERR_LABEL = 1, 2            # ETP_MLM_ERR_* of include/etpnav_hip.h
 
 
 class MlmStep(_Staging):
     def __init__(self, model: GlocalTextPathNavCMT, batch: Dict[str, torch.Tensor], dropout=None, drop_seed: int = 0,
-                 overlap: bool = True, traj_nodes=None):
+                 overlap: bool = True, traj_nodes=None, select: Optional[str] = None, capacity=None):
         """batch: etpnav_amd.synthetic.make_sap_batch layout + ``txt_labels`` [B,L] (-1 = not masked, else the token id).
         dropout: None, "config" (the model config's rates; no drop_env in this task) or (p_hidden, p_attn, p_head, p_env).
         overlap: the three-stream schedule of PlannerStep -- weight gradients on an `aux` stream, the panorama branch
         (forward and backward) on `s2` beside the text branch; False = everything on the caller's stream.
-        traj_nodes: as PlannerStep's (node features from the batch's descriptor tables; check_traj())."""
+        traj_nodes: as PlannerStep's (node features from the batch's descriptor tables; check_traj()).
+        select: where the masked-row gather (and its transpose for the backward) is built -- None / "device": etp_mlm_select
+        (csrc/traj_batch.hip) at staging time, on the stream the step runs on, from ``batch.mlm_dev`` (a loader's int32 labels on the
+        device with the host-known count) or from one int32 upload of the host ``txt_labels``; check_select() reads what it flagged.
+        "host" or ETP_MLM_SELECT=0 (read once, here): torch.nonzero / cumsum on the host and six small uploads.  Same bits.
+        capacity: as PlannerStep's, with Nm (the masked tokens) as a sixth key."""
         if not model._engine.cconf.use_lang2visn:
             raise _lib.EtpError("the MLM task needs a model built with use_lang2visn_attn=True (pre-training config)")
-        self._stage(model, batch, N_MLM_INPUTS, dropout, drop_seed, 0.0, traj_nodes)
+        if select not in (None, "device", "host"):
+            raise ValueError(f"select: None, 'device' or 'host' (got {select!r})")
+        self.select = "host" if select == "host" or os.environ.get("ETP_MLM_SELECT", "1") == "0" else "device"
+        self._stage(model, batch, N_MLM_INPUTS, dropout, drop_seed, 0.0, traj_nodes, capacity)
         # gradient accumulation (PretrainDriver): later micro-steps keep the arena (zero_grads False) and every micro-step's mean
         # loss is scaled by 1 / accumulation steps (train_r2r.py:250-252)
         self.zero_grads, self.loss_scale = True, 1.0
-        eng, dev, (B, Lt, G) = self.eng, self.eng.device, (self.B, self.Lt, self.G)
-        self.dims = (B, Lt, self.Bp, self.V, G, eng.cconf.hidden)
-        # masked positions: row gather of the text (and its transpose for the backward)
+        self.aux, self.s2 = (_new_stream(self.L), _new_stream(self.L)) if overlap else (None, None)
+
+    def _dims_of(self, batch):
+        """the batch's dimensions with Nm, the host-known number of masked tokens"""
+        d = super()._dims_of(batch)
+        md = getattr(batch, "mlm_dev", None) if self.select == "device" else None
+        d["Nm"] = int(md["n_masked"]) if md is not None else int((batch["txt_labels"] != -1).sum())
+        if d["Nm"] == 0:
+            raise ValueError("no masked tokens in the batch")
+        return d
+
+    def _byte_buffers(self, d):
+        b = super()._byte_buffers(d)
+        b.update({"st_mlm": self.L.etp_mlm_stash_bytes(self.eng.handle, d["B"], d["L"], d["G"], d["Nm"]),
+                  "ws_mlm": self.L.etp_mlm_ws_bytes(self.eng.handle, d["B"], d["L"], d["G"], d["Nm"])})
+        return b
+
+    def _int_arrays(self, d):
+        a = super()._int_arrays(d)
+        n, Nm = d["B"] * d["L"], d["Nm"]
+        a.update({"row_nll": ((Nm,), torch.float32), "row_pred": ((Nm,), torch.int32)})    # run_eval's per-row outputs
+        if self.select == "device":
+            a.update({"_lab": ((n,), torch.int32), "_rows": ((Nm,), torch.int32), "_ptr_t": ((n + 1,), torch.int32),
+                      "labels": ((Nm,), torch.int64), "_arange": ((Nm + 1,), torch.int32), "_ones": ((Nm,), torch.float32),
+                      "sel_status": ((2,), torch.int32)})
+        return a
+
+    def _bind(self, batch, first: bool = False):
+        new = super()._bind(batch, first)
+        self.Nm = self._d["Nm"]
+        self.dims = (self.B, self.Lt, self.Bp, self.V, self.G, self.eng.cconf.hidden)
+        self._select(batch, new)
+        return new
+
+    def _select(self, batch, new=()):
+        """the selection of `batch`: an input of the step like traj_dev, built when the batch is staged and never inside _enqueue
+        (no kernel of the step takes an index from a buffer the step produces).  `new`: the arrays whose allocation is new."""
+        Nm = self.Nm
+        if self.select == "host":
+            self._select_host(batch)
+            return
+        # arange and ones are written once per allocation, over all of it: the views of a later batch are prefixes
+        for k, fill in (("_arange", lambda t: torch.arange(t.numel(), dtype=torch.int32, out=t)), ("_ones", lambda t: t.fill_(1.0))):
+            if k in new:
+                fill(self._pool[k].view(getattr(self, k).dtype) if self._pool is not None else getattr(self, k))
+        if "sel_status" in new:
+            self.sel_status.zero_()
+        md = getattr(batch, "mlm_dev", None)
+        n = self.B * self.Lt
+        if md is not None:
+            lab = md["txt_labels"]
+            if tuple(lab.shape) != (self.B, self.Lt) or lab.dtype != torch.int32 or not lab.is_contiguous() or \
+                    lab.device != self._rows.device:
+                raise ValueError(f"mlm_dev['txt_labels'] is a contiguous int32 tensor {(self.B, self.Lt)} on the step's device "
+                                 f"(got {tuple(lab.shape)}, {lab.dtype})")
+        else:
+            lab = self._lab
+            lab.copy_(batch["txt_labels"].reshape(-1).to(torch.int32), non_blocking=True)
+        self._lab_src = lab                    # taken by reference until the next load, like traj_dev
+        self.sel = (self._arange, self._rows, self._ones)
+        self.selT = (self._ptr_t, self._arange[:Nm], self._ones)
+        cap = self._pool["_rows"].numel() // 4 if self._pool is not None else Nm
+        check(self.L.etp_mlm_select(ptr(lab), n, self.eng.cconf.vocab, Nm, cap, ptr(self._rows), ptr(self._ptr_t), ptr(self.labels),
+                                    ptr(self.sel_status), self.eng.stream()), "mlm_select")
+
+    def _select_host(self, batch):
+        """masked positions: row gather of the text (and its transpose for the backward), built on the host"""
+        dev, Nm = self.eng.device, self.Nm
         sel = (batch["txt_labels"] != -1).reshape(-1)
         rows = torch.nonzero(sel).reshape(-1).to(torch.int32)
-        Nm = self.Nm = int(rows.numel())
-        if Nm == 0:
-            raise ValueError("no masked tokens in the batch")
         i32 = lambda x: torch.as_tensor(x, dtype=torch.int32).to(dev)
         self.sel = (i32(torch.arange(Nm + 1)), rows.to(dev), torch.ones(Nm, dtype=torch.float32, device=dev))
-        ptr_t = torch.zeros(B * Lt + 1, dtype=torch.int32)
+        ptr_t = torch.zeros(self.B * self.Lt + 1, dtype=torch.int32)
         ptr_t[1:] = torch.cumsum(sel.to(torch.int32), 0)
         self.selT = (ptr_t.to(dev), i32(torch.arange(Nm)), torch.ones(Nm, dtype=torch.float32, device=dev))
         self.labels = batch["txt_labels"].reshape(-1)[sel].to(torch.int64).contiguous().to(dev)
-        self.st_mlm = eng.buf(self.L.etp_mlm_stash_bytes(eng.handle, B, Lt, G, Nm))
-        self.ws_mlm = eng.buf(self.L.etp_mlm_ws_bytes(eng.handle, B, Lt, G, Nm))
-        self.aux, self.s2 = (_new_stream(self.L), _new_stream(self.L)) if overlap else (None, None)
-        self.row_nll = self.row_pred = None    # run_eval's per-row outputs, allocated at its first call
+
+    def load_batch(self, batch: Dict[str, torch.Tensor]):
+        """Refill the step with another batch and build its selection, on the stream the step runs on.  A step built without
+        `capacity` takes the SAME shapes only (the masked count included); one built with it takes any (_Staging._bind)."""
+        if self._pool is None and self.batch_shape_key(batch) != self.shape_key():
+            raise ValueError(f"batch shapes {self.batch_shape_key(batch)} differ from this step's {self.shape_key()}")
+        if self._pool is None:
+            for k, src, dt in INPUTS[:N_MLM_INPUTS]:
+                self.inp[k].copy_(batch[src].to(dt), non_blocking=True)
+            self._select(batch)
+        else:
+            self._bind(batch)
+        self._load_nodes(batch)
+
+    def check_select(self) -> None:
+        """one device-to-host copy of etp_mlm_select's status words; raises EtpError naming the flags, the count the kernel found and
+        the count the step was sized for.  The step itself never synchronises; a step on the host route has nothing to check."""
+        if self.select != "device":
+            return
+        flags, count = (int(x) for x in self.sel_status.cpu().tolist())
+        if flags:
+            names = [n for n, bit in (("ETP_MLM_ERR_COUNT", MLM_ERR_COUNT), ("ETP_MLM_ERR_LABEL", MLM_ERR_LABEL)) if flags & bit]
+            raise _lib.EtpError(f"etp_mlm_select flagged {' | '.join(names)}: {count} entries of txt_labels are masked, the step was "
+                                f"sized for n_masked = {self.Nm} (vocabulary {self.eng.cconf.vocab})")
 
     @staticmethod
     def batch_shape_key(batch):
@@ -80,9 +173,6 @@ class MlmStep(_Staging):
         """validate_mlm's loop body (train_r2r.py:362-368) on this batch: the schedule of ``run_eager(backward=False)`` with
         etp_mlm_eval in place of etp_mlm_fwd -- per-row nll / arg-max into ``row_nll`` / ``row_pred``, their sums added to
         `counters` (etpnav_amd.validate.EvalCounters) on the device.  No loss, no dlogits, no host read."""
-        if self.row_nll is None:
-            self.row_nll = torch.empty(self.Nm, dtype=torch.float32, device=self.eng.device)
-            self.row_pred = torch.empty(self.Nm, dtype=torch.int32, device=self.eng.device)
         self.step_no += 1
         try:
             with self.eng.scope(aux=self.aux, aux2=None, lazy=0, drop=self._drop_state()):
@@ -214,16 +304,22 @@ class PretrainDriver:
     reference's decay grouping and gradient clipping (optim/misc.py, optim/adamw.py, train_r2r.py:283-300).
 
     Step objects (preallocated stash / workspace / streams) are cached per batch shape and refilled in place for SAP; the MLM
-    step is rebuilt per batch (its masked-token count changes the buffer plan)."""
+    step is rebuilt per batch (its masked-token count changes the buffer plan).  With reuse_steps=True one capacity step object per
+    task serves the whole run instead (and one more pair validate()): load_batch of any shape, no synchronise per batch."""
 
     def __init__(self, model: GlocalTextPathNavCMT, loaders: Dict, learning_rate: float = 5e-5, warmup_steps: int = 10000,
                  num_train_steps: int = 100000, grad_norm: float = 5.0, accum_steps: int = 1, dropout="config", seed: int = 0,
-                 distributed: bool = False, max_cached_steps: int = 4, generator=None, max_txt_len: int = 100):
+                 distributed: bool = False, max_cached_steps: int = 4, generator=None, max_txt_len: int = 100,
+                 reuse_steps: bool = False, batch_size: Optional[int] = None):
         """accum_steps = gradient_accumulation_steps of train_r2r.py:231-300: that many consecutive (task, batch) draws (the
         MetaLoader keeps the task fixed over them, loader.py:61-63) each add the gradient of mean-loss / accum_steps to the
         arena, then ONE reduction / clipping / optimizer step follows.  max_txt_len = the dataset's truncation length
         (run_pt/r2r_pretrain_habitat.json: 100): with several ranks the row-sparse word-embedding exchange uses the
-        rank-independent capacity B * max_txt_len (the collate pads to the per-batch maximum, so L differs across ranks)."""
+        rank-independent capacity B * max_txt_len (the collate pads to the per-batch maximum, so L differs across ranks).
+        reuse_steps: one capacity PlannerStep and one capacity MlmStep serve training for the whole run and one more pair serves
+        validate() (step.py _Staging: load_batch of any shape), instead of the per-shape cache and the per-batch MlmStep; the initial
+        capacity is B = batch_size (default: the loaders' ``batch_size`` attribute, else the first batch) and L = max_txt_len, the rest
+        grows on demand.  Nothing synchronises per batch; check_select() / check_traj() run at the validation points and in close()."""
         from .optim import FusedAdamW, WarmupLinearLR
         from . import dp
         if accum_steps < 1:
@@ -242,6 +338,12 @@ class PretrainDriver:
         self._sap = {}                      # shape key -> PlannerStep
         self._sap_eval = {}                 # shape key -> PlannerStep of validate(): no dropout, apart from the training cache
         self._max = max_cached_steps
+        self.reuse_steps = bool(reuse_steps)
+        self._reused = {}                   # (task, training?) -> the one capacity step object of that role
+        if batch_size is None:
+            sizes = [getattr(spec[0] if isinstance(spec, tuple) else spec, "batch_size", None) for spec in loaders.values()]
+            batch_size = max([int(b) for b in sizes if b], default=0)
+        self._capacity = {"L": self.max_txt_len, **({"B": int(batch_size)} if batch_size else {})}
         self.reducers = {}
         if distributed:
             for task in ("sap", "mlm"):
@@ -251,8 +353,32 @@ class PretrainDriver:
         self.lr_history = []
         self.val_logs = []                  # (global_step, dict) of every validation point of run()
 
+    def _reused_step(self, task: str, train: bool, batch):
+        """reuse_steps: the one step object of (task, training / validation), built at the first batch and refilled ever after"""
+        from .step import PlannerStep
+        st = self._reused.get((task, train))
+        if st is not None:
+            st.load_batch(batch)
+            return st
+        kw = dict(dropout=self.dropout, drop_seed=self.seed) if train else dict(dropout=None)
+        if task == "sap":
+            st = PlannerStep(self.model, batch, zero_grads=train, grad_overwrite=False, capacity=self._capacity, **kw)
+        else:
+            st = MlmStep(self.model, batch, capacity=self._capacity, **kw)
+        self._reused[(task, train)] = st
+        return st
+
+    def check_steps(self) -> None:
+        """reuse_steps: what the reused steps' status words hold (check_select / check_traj): one small copy per step object"""
+        for st in self._reused.values():
+            st.check_traj()
+            if isinstance(st, MlmStep):
+                st.check_select()
+
     def _sap_step(self, batch):
         from .step import PlannerStep
+        if self.reuse_steps:
+            return self._reused_step("sap", True, batch)
         key = PlannerStep.batch_shape_key(batch)
         st = self._sap.get(key)
         if st is None:
@@ -283,7 +409,8 @@ class PretrainDriver:
                 raise ValueError(f"instruction length {st.Lt} exceeds max_txt_len={self.max_txt_len} (the exchange capacity)")
             self._touched.append((st.inp["txt_ids"].reshape(-1).clone() if A > 1 else st.inp["txt_ids"].reshape(-1), st.B))
         elif task == "mlm":
-            st = MlmStep(self.model, batch, dropout=self.dropout, drop_seed=self.seed)
+            st = self._reused_step("mlm", True, batch) if self.reuse_steps else \
+                MlmStep(self.model, batch, dropout=self.dropout, drop_seed=self.seed)
             st.step_no = self.global_step * A + self._micro
             st.zero_grads = first
             st.loss_scale = 1.0 / A
@@ -294,7 +421,7 @@ class PretrainDriver:
         self._micro += 1
         self.task_losses.setdefault(name, []).append(loss)
         if self._micro < A:
-            if task == "mlm":
+            if task == "mlm" and not self.reuse_steps:
                 torch.cuda.current_stream().synchronize()
                 st.close()
             return loss
@@ -311,13 +438,15 @@ class PretrainDriver:
         self.global_step += 1
         self.lr_history.append(self.sched.step(self.global_step))
         self.opt.step()
-        if task == "mlm":
+        if task == "mlm" and not self.reuse_steps:
             torch.cuda.current_stream().synchronize()      # the per-batch MLM step object is released: its buffers must be idle
             st.close()
         return loss
 
     def _sap_eval_step(self, batch):
         from .step import PlannerStep
+        if self.reuse_steps:
+            return self._reused_step("sap", False, batch)
         key = PlannerStep.batch_shape_key(batch)
         st = self._sap_eval.get(key)
         if st is None:
@@ -349,6 +478,8 @@ class PretrainDriver:
                     st = self._sap_eval_step(batch)
                     st.run_eager(backward=False)
                     sap_eval(st, counters)
+                elif self.reuse_steps:
+                    self._reused_step("mlm", False, batch).run_eval(counters)
                 else:
                     st = MlmStep(self.model, batch, dropout=None)
                     st.run_eval(counters)
@@ -359,6 +490,7 @@ class PretrainDriver:
             keys = ("loss", "acc") if task == "mlm" else ("gloss", "gacc")
             log = {keys[0]: loss_sum / n_rows, keys[1]: n_correct / n_rows, "tok_per_s": n_rows / dt}
             out.update({f"val{setname}_{name}_{k}": v for k, v in log.items()})
+        self.check_steps()                  # the validation point's check of the training and validation steps' status words
         return out
 
     def run(self, num_steps: int, valid_steps: Optional[int] = None, val_loaders=None, val2_loaders=None, on_checkpoint=None):
@@ -388,7 +520,13 @@ class PretrainDriver:
             on_checkpoint(self.global_step)
 
     def close(self):
-        for st in list(self._sap.values()) + list(self._sap_eval.values()):
-            st.close()
-        self._sap.clear()
-        self._sap_eval.clear()
+        try:
+            if self._reused:
+                torch.cuda.synchronize(self.model._engine.device)
+                self.check_steps()
+        finally:
+            for st in list(self._sap.values()) + list(self._sap_eval.values()) + list(self._reused.values()):
+                st.close()
+            self._sap.clear()
+            self._sap_eval.clear()
+            self._reused.clear()

@@ -345,8 +345,10 @@ class TrajBatch(dict):
     """The batch dict of the native loaders -- keys and values as before -- with the trajectory's integer tables on the device beside it:
     ``traj_dev`` = {step_off [B+1], step_vp [R], cand_count [R], cand_vp [R, Kmax], gmap_id [B, G], gmap_len [B]} int32 views of the
     batch's one staging buffer, plus ``Kmax``.  PlannerStep / MlmStep compute the node features from them (etp_traj_nodes_fwd / _bwd)
-    and build no CSR from ``traj``'s string lists."""
+    and build no CSR from ``traj``'s string lists.  An MLM batch also carries ``mlm_dev`` = {txt_labels: int32 [B, L] on the device (-1 =
+    not masked), n_masked: the host-known count}, a view of the same buffer: MlmStep builds its row gather from it (etp_mlm_select)."""
     traj_dev: Optional[dict] = None
+    mlm_dev: Optional[dict] = None
 
 
 class _Batches:
@@ -402,11 +404,13 @@ class _Batches:
                 ("cand_vp", np.int32, (R, Kmax)), ("txt_ids", np.int64, (B, L)),
                 ("txt_masks", np.bool_, (B, L)), ("gmap_step_ids", np.int64, (B, G)), ("gmap_pos_fts", np.float32, (B, G, 7)),
                 ("gmap_visited_masks", np.bool_, (B, G)), ("labels", np.int64, (B,))]
+        if txt_labels is not None:                                               # what etp_mlm_select reads: rides in the same copy
+            segs.append(("mlm_labels", np.int32, (B, L)))
         offs, total = {}, 0
         for name, dt, shape in segs:
             offs[name] = total
             total += _align(int(np.prod(shape)) * np.dtype(dt).itemsize)
-        stage = torch.zeros(total, dtype=torch.uint8, pin_memory=True)            # pad_sequence / pad_tensors: zero padding
+        stage = torch.zeros(total, dtype=torch.uint8, pin_memory=self.device.type == "cuda")    # pad_sequence / pad_tensors: zero padding
         host = stage.numpy()
         h = {name: host[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape)
              for name, dt, shape in segs}
@@ -435,6 +439,10 @@ class _Batches:
             h["gmap_pos_fts"][b, :g] = rec["gmap_pos_fts"]
             h["gmap_visited_masks"][b, :g] = rec["gmap_visited_masks"]
         h["labels"][:] = labels
+        if txt_labels is not None:
+            h["mlm_labels"][:] = -1
+            for b, t in enumerate(txt_labels):
+                h["mlm_labels"][b, :len(t)] = t
         dev = stage.to(self.device, non_blocking=True)                           # the ONE host-to-device copy
         torch_dt = {np.int32: torch.int32, np.int64: torch.int64, np.float32: torch.float32, np.bool_: torch.bool}
         d = {name: dev[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(torch_dt[dt]).view(shape)
@@ -462,12 +470,14 @@ class _Batches:
                     "traj": {"traj_step_lens": [len(r["rows"]) for r in recs], "traj_vp_lens": [list(r["view_lens"]) for r in recs],
                              "traj_vpids": [r["traj_vpids"] for r in recs], "traj_cand_vpids": [r["traj_cand_vpids"] for r in recs],
                              "gmap_vpids": [r["gmap_vpids"] for r in recs]}})
-        if txt_labels is not None:                                               # host: MlmStep builds its row gather from it
+        if txt_labels is not None:                                               # host: the fallback route of MlmStep (select="host")
             tl = torch.full((B, L), -1, dtype=torch.int64)
             for b, t in enumerate(txt_labels):
                 tl[b, :len(t)] = torch.from_numpy(t)
             out["txt_labels"] = tl
         out = TrajBatch(out)
+        if txt_labels is not None:                                               # mask_tokens ran on the host: the count is known here
+            out.mlm_dev = {"txt_labels": d["mlm_labels"], "n_masked": int((h["mlm_labels"] != -1).sum())}
         out.traj_dev = {"step_off": d["step_off"], "step_vp": d["step_vp"], "cand_count": d["cand_count"], "cand_vp": d["cand_vp"],
                         "gmap_id": d["gmap_idx"], "gmap_len": d["gmap_len"], "Kmax": Kmax}
         return out

@@ -89,15 +89,113 @@ INPUTS = (("txt_ids", "txt_ids", torch.int64), ("txt_masks", "txt_masks", torch.
           ("gmask", "gmap_masks", torch.bool),
           ("visited", "gmap_visited_masks", torch.bool), ("dists", "gmap_pair_dists", torch.float32), ("labels", "labels", torch.int64))
 N_MLM_INPUTS = 10
+# the axes of every input in terms of a step's dimensions ('*' = a feature width, taken from the batch): what a capacity step sizes
+# its input allocations by
+INPUT_AXES = {"txt_ids": "BL", "txt_masks": "BL", "rgb": "RV*", "dep": "RV*", "loc": "RV*", "nav": "RV", "view_lens": "R", "step_ids": "BG",
+              "pos": "BG*", "gmask": "BG", "visited": "BG", "dists": "BGG", "labels": "B"}
+CAPACITY_KEYS = ("B", "L", "R", "V", "G", "Nm")
 
 
 class _Staging:
     """What PlannerStep and MlmStep (pretrain.py) stage alike -- device inputs, node CSR, the API tensors and stash / workspace of the
     text and panorama branches, dropout state -- and the library calls both issue with the same arguments.  The two schedules
-    themselves (which stream, which order) stay written out in each class."""
+    themselves (which stream, which order) stay written out in each class.
+
+    A step built with ``capacity`` (a dict with any of B, L, R, V, G, Nm, or True = the first batch) keeps every one of these in an
+    allocation sized for the capacity; the step's tensors are contiguous views of the current batch's shape at offset 0 of them, and
+    ``load_batch`` accepts any shape: every entry point of the library recomputes its buffer plan from the dimensions it is called
+    with, so a buffer that is large enough serves any smaller shape.  ``regrows`` counts the loads that had to enlarge something."""
+
+    def _dims_of(self, batch) -> Dict[str, int]:
+        B, L = batch["txt_ids"].shape
+        R, V = batch["rgb_fts"].shape[:2]
+        return {"B": int(B), "L": int(L), "R": int(R), "V": int(V), "G": int(batch["gmap_step_ids"].shape[1])}
+
+    def _api_tensors(self, d):
+        """name -> shape of the fp32 API tensors (pmask: bool) at the dimensions d"""
+        B, L, R, V, G, H = d["B"], d["L"], d["R"], d["V"], d["G"], self.eng.cconf.hidden
+        return {"txt": (B, L, H), "pano": (R, V, H), "pmask": (R, V), "gimg": (B, G, H), "d_txt": (B, L, H), "d_gimg": (B, G, H),
+                "d_pano": (R, V, H)}
+
+    def _byte_buffers(self, d):
+        """name -> bytes of the stash / workspace buffers at the dimensions d, as the library plans them.  Separate backward
+        workspaces: the backward passes may run on parallel streams."""
+        L_, h = self.L, self.eng.handle
+        return {"st_txt": L_.etp_txt_stash_bytes(h, d["B"], d["L"]), "ws_txt": L_.etp_txt_ws_bytes(h, d["B"], d["L"]),
+                "st_pano": L_.etp_pano_stash_bytes(h, d["R"], d["V"]), "ws_pano": L_.etp_pano_ws_bytes(h, d["R"], d["V"])}
+
+    def _int_arrays(self, d):
+        """name -> (shape, dtype) of the integer arrays the step owns"""
+        return {"traj_status": ((d["B"] * d["G"] + d["R"],), torch.int32)} if self.traj_nodes else {}
+
+    def _plan(self, d, batch):
+        """name -> (bytes, shape, dtype) of everything the step allocates at the dimensions d; shape None = a byte buffer"""
+        plan = {}
+        for k, src, dt in INPUTS[:self._n_inputs] if self._pool is not None else ():
+            t = batch[src]
+            shape = tuple(d[a] if a != "*" else int(t.shape[n]) for n, a in enumerate(INPUT_AXES[k]))
+            plan["in:" + k] = (shape, dt)
+        plan.update({k: (s, torch.bool if k == "pmask" else torch.float32) for k, s in self._api_tensors(d).items()})
+        plan.update(self._int_arrays(d))
+        out = {}
+        for k, (shape, dt) in plan.items():
+            n = 1
+            for x in shape:
+                n *= x
+            out[k] = (n * torch.empty((), dtype=dt).element_size(), shape, dt)
+        for k, nbytes in self._byte_buffers(d).items():
+            if nbytes < 0:
+                raise _lib.EtpError(f"{k}: the library plans no buffer for the dimensions {d}")
+            out[k] = (int(nbytes), None, None)
+        return out
+
+    def _bind(self, batch, first: bool = False):
+        """(re)point the step's tensors at `batch`'s dimensions.  A capacity step views its allocations, enlarging (never shrinking)
+        whatever the library's byte queries for the new dimensions find short -- one device synchronise per such load, since the
+        side streams of the step that last used the old allocation are not torch's.  -> the names whose allocation is new."""
+        d = self._d = self._dims_of(batch)
+        for k, src, _ in INPUTS[:self._n_inputs] if self._pool is not None else ():
+            want = tuple(d[a] if a != "*" else int(batch[src].shape[n]) for n, a in enumerate(INPUT_AXES[k]))
+            if tuple(batch[src].shape) != want:
+                raise ValueError(f"batch[{src!r}] has shape {tuple(batch[src].shape)}, the batch's dimensions {d} make it {want}")
+        self.B, self.Lt, self.Bp, self.V, self.G = d["B"], d["L"], d["R"], d["V"], d["G"]
+        need = self._plan(d, batch)
+        dev, new = self.eng.device, []
+        if self._pool is None:                 # today's exact allocations
+            for k, (nbytes, shape, dt) in need.items():
+                if k.startswith("in:"):
+                    continue
+                setattr(self, k, self.eng.buf(nbytes) if shape is None else torch.empty(shape, dtype=dt, device=dev))
+                new.append(k)
+            self.inp = {k: batch[src].to(dt).contiguous().to(dev) for k, src, dt in INPUTS[:self._n_inputs]}
+        else:
+            short = [k for k, (nbytes, _, _) in need.items() if k not in self._pool or self._pool[k].numel() < nbytes]
+            if short:
+                self._cap = {k: max(self._cap.get(k, 0), v) for k, v in d.items()}
+                at_cap = self._plan(self._cap, batch)
+                if not first:
+                    torch.cuda.synchronize(dev)
+                    self.regrows += 1
+                for k in short:
+                    self._pool[k] = self.eng.buf(max(need[k][0], at_cap[k][0], 1))
+                new = short
+            self.inp = getattr(self, "inp", None) or {}
+            for k, (nbytes, shape, dt) in need.items():
+                t = self._pool[k][:nbytes]
+                if shape is not None:
+                    t = t.view(dt).view(shape)
+                if k.startswith("in:"):
+                    self.inp[k[3:]] = t
+                else:
+                    setattr(self, k, t)
+            for k, src, dt in INPUTS[:self._n_inputs]:
+                self.inp[k].copy_(batch[src].to(dt), non_blocking=True)
+        if self.traj_nodes:                    # forward [B*G] node rows, backward [Bp] steps; a forward-only step leaves the latter alone
+            self.traj_status.zero_()
+        return new
 
     def _stage(self, model: GlocalTextPathNavCMT, batch, n_inputs: int, dropout, drop_seed: int, p_env: float,
-               traj_nodes: Optional[bool] = None):
+               traj_nodes: Optional[bool] = None, capacity=None):
         self.model = model
         eng = self.eng = model._engine
         eng.require_gpu()
@@ -105,30 +203,23 @@ class _Staging:
         if dropout == "config":                # the model config's rates, the reference's policy.train()
             dropout = config_dropout_rates(model.config) + (float(p_env),)
         self.dropout, self.drop_seed, self.step_no = dropout, int(drop_seed) & 0xFFFFFFFF, 0
-        B, Lt = self.B, self.Lt = batch["txt_ids"].shape
-        # Panorama batch: B (one panorama per episode) or the sum of trajectory steps; the node features are a CSR gather over all
-        # panorama embeddings either way.
-        Bp, V = self.Bp, self.V = batch["rgb_fts"].shape[:2]
-        G = self.G = batch["gmap_step_ids"].shape[1]
-        dev, H, h = eng.device, eng.cconf.hidden, eng.handle
-        self.inp = {k: batch[src].to(dt).contiguous().to(dev) for k, src, dt in INPUTS[:n_inputs]}
+        self._n_inputs, self.regrows = n_inputs, 0
+        if capacity is None or capacity is False:
+            self._pool = self._cap = None
+        else:
+            cap = {} if capacity is True else dict(capacity)
+            if any(k not in CAPACITY_KEYS for k in cap):
+                raise ValueError(f"capacity: a dict with any of {CAPACITY_KEYS} or True (got {sorted(cap)})")
+            self._pool, self._cap = {}, {k: int(v) for k, v in cap.items()}
         # node features of a trajectory batch straight from its integer tables (etp_traj_nodes_fwd / _bwd, csrc/traj_batch.hip): whenever
         # the batch carries them (TrajBatch.traj_dev of the native loaders), or forced for a string-only batch; ETP_TRAJ_NODES=0 (read
         # once, here) or traj_nodes=False keep the host-built CSR + etp_gather_sum
         self.traj_nodes = traj_nodes is not False and os.environ.get("ETP_TRAJ_NODES", "1") != "0" and \
             (getattr(batch, "traj_dev", None) is not None or bool(traj_nodes))
         self.traj_dev = self.csr_f = self.csr_b = None
-        if self.traj_nodes:
-            self.traj_status = torch.zeros(B * G + Bp, dtype=torch.int32, device=dev)    # forward [B*G] node rows, backward [Bp] steps
+        self.loss = torch.zeros(1, dtype=torch.float32, device=eng.device)
+        self._bind(batch, first=True)
         self._load_nodes(batch)
-        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)   # API tensors are fp32 in both modes
-        self.txt, self.pano, self.pmask, self.gimg = e(B, Lt, H), e(Bp, V, H), e(Bp, V, dt=torch.bool), e(B, G, H)
-        self.d_txt, self.d_gimg, self.d_pano = e(B, Lt, H), e(B, G, H), e(Bp, V, H)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        # separate backward workspaces: the backward passes may run on parallel streams
-        self.st_txt, self.ws_txt = eng.buf(self.L.etp_txt_stash_bytes(h, B, Lt)), eng.buf(self.L.etp_txt_ws_bytes(h, B, Lt))
-        self.st_pano, self.ws_pano = eng.buf(self.L.etp_pano_stash_bytes(h, Bp, V)), eng.buf(self.L.etp_pano_ws_bytes(h, Bp, V))
-        return e                               # the allocator, for the tensors only one of the two steps has
 
     def _drop_state(self):
         if self.dropout is None:
@@ -215,7 +306,7 @@ class PlannerStep(_Staging):
     def __init__(self, model: GlocalTextPathNavCMT, batch: Dict[str, torch.Tensor], overlap: bool = True,
                  dropout=None, drop_seed: int = 0, refresh_weights: bool = True, zero_grads: bool = True,
                  grad_overwrite: Optional[bool] = None, share_side_streams: Optional["PlannerStep"] = None,
-                 traj_nodes: Optional[bool] = None):
+                 traj_nodes: Optional[bool] = None, capacity=None):
         """dropout: None (eval-mode step), "config" (the model config's rates, the reference's policy.train()), or a
         tuple (p_hidden, p_attn, p_head, p_env).  refresh_weights / zero_grads = False when etpnav_amd.optim.FusedAdamW
         closes the step: its kernel already wrote the bf16 weight shadow and zeroed the gradient arena.
@@ -225,7 +316,9 @@ class PlannerStep(_Staging):
         language-side x-layer weights this step does not touch).
         traj_nodes: None = the node features come from the batch's descriptor tables when it carries them (a loader's TrajBatch), else
         from the host-built CSR; True forces the tables for a string-only batch['traj'] (graph_inputs.traj_descriptors); False or
-        ETP_TRAJ_NODES=0 keep the CSR.  check_traj() reads what the table route flagged."""
+        ETP_TRAJ_NODES=0 keep the CSR.  check_traj() reads what the table route flagged.
+        capacity: None = buffers of exactly this batch's shape and a same-shape load_batch; a dict with any of B, L, R, V, G, or True
+        (this batch), = one step object for batches of any shape (_Staging)."""
         self.refresh_weights, self.zero_grads = refresh_weights, zero_grads
         # frozen sub-models (vlnbert_init.py:51-54 -> vilmodel_cmt.py:422-433,675-682): with fix_lang_embedding the text encoder's
         # output is detached (LanguageEncoder.forward :431-432) -- no text backward runs and no gradient reaches `embeddings.*` /
@@ -240,12 +333,9 @@ class PlannerStep(_Staging):
             grad_overwrite = bool(zero_grads) and not model._engine.cconf.use_lang2visn and \
                 os.environ.get("ETP_GRAD_OVERWRITE", "1") != "0"
         self.grad_overwrite = bool(grad_overwrite)
-        e = self._stage(model, batch, len(INPUTS), dropout, drop_seed, model.drop_env_prob, traj_nodes)
+        self._stage(model, batch, len(INPUTS), dropout, drop_seed, model.drop_env_prob, traj_nodes, capacity)
         self.loss_scale = 1.0 / self.B                         # cross_entropy(sum) / batch_size (ss_trainer_ETP.py:892)
-        eng, h, (B, Lt, G) = self.eng, self.eng.handle, (self.B, self.Lt, self.G)
-        self.gemb, self.logits, self.dlogits = e(B, G, eng.cconf.hidden), e(B, G), e(B, G)
-        self.st_nav = eng.buf(self.L.etp_nav_stash_bytes(h, B, Lt, G))
-        self.ws_nav = eng.buf(self.L.etp_nav_ws_bytes(h, B, Lt, G))
+        eng = self.eng
         # side streams: `aux` carries the weight-gradient GEMMs, `s2` the panorama branch (independent of the text branch), `aux2`
         # the d txt_embeds chain of the navigation backward
         self.overlap = overlap
@@ -278,6 +368,23 @@ class PlannerStep(_Staging):
         self.graphs = []
         self.stream = None
 
+    def _api_tensors(self, d):
+        t = super()._api_tensors(d)
+        t.update({"gemb": (d["B"], d["G"], self.eng.cconf.hidden), "logits": (d["B"], d["G"]), "dlogits": (d["B"], d["G"])})
+        return t
+
+    def _byte_buffers(self, d):
+        b = super()._byte_buffers(d)
+        b.update({"st_nav": self.L.etp_nav_stash_bytes(self.eng.handle, d["B"], d["L"], d["G"]),
+                  "ws_nav": self.L.etp_nav_ws_bytes(self.eng.handle, d["B"], d["L"], d["G"])})
+        return b
+
+    def _int_arrays(self, d):
+        a = super()._int_arrays(d)
+        if self._pool is not None:             # validate.sap_eval's per-row outputs (it allocates them itself for a fixed-shape step)
+            a.update({"row_nll": ((d["B"],), torch.float32), "row_pred": ((d["B"],), torch.int32)})
+        return a
+
     def _scope(self, lazy: Optional[int] = None):
         """The planner handle is shared by every step object of a model (PretrainDriver alternates MlmStep and several cached
         PlannerSteps): side streams, lazy-join level, dropout state and overwrite mode are (re)installed at every enqueue, so a
@@ -298,7 +405,15 @@ class PlannerStep(_Staging):
     def load_batch(self, batch: Dict[str, torch.Tensor]):
         """Refill the preallocated device inputs with another batch of the SAME shapes (the stash / workspace buffers and the
         streams are reused; only the small CSR index arrays of the node aggregation are rebuilt, or, on the table route, the new
-        batch's descriptor tensors are taken by reference)."""
+        batch's descriptor tensors are taken by reference).  A step built with `capacity` takes a batch of any shape (_Staging._bind):
+        its tensors are re-viewed at the new dimensions and whatever is short grows."""
+        if self._pool is not None:
+            if self.graphs:
+                raise RuntimeError("load_batch() on a step with captured / recorded graphs: close() the graphs (or build a new step) first")
+            self._bind(batch)
+            self._load_nodes(batch)
+            self.loss_scale = 1.0 / self.B     # as a step built for this batch has it; a caller's own scale is set after the load
+            return
         if self.batch_shape_key(batch) != self.shape_key():
             raise ValueError(f"batch shapes {self.batch_shape_key(batch)} differ from this step's {self.shape_key()}")
         if self.graphs:

@@ -1114,6 +1114,29 @@ int etp_traj_nodes_bwd(const float* d_gmap_img_fts, const int32_t* step_off, con
                        const int32_t* cand_count, const int32_t* cand_vp, const int32_t* gmap_id, const int32_t* gmap_len, int B, int R,
                        int V, int Kmax, int G, int H, float* d_pano, int32_t* status, etp_stream_t stream);
 
+/* The MLM task's masked-row selection on the device (csrc/traj_batch.hip): what _compute_masked_hidden and the label gather of
+ * pretrain_cmt.py:141-163 select, as the index arrays etp_mlm_fwd / etp_mlm_eval / etp_mlm_bwd read -- the host build of
+ * pretrain.MlmStep.__init__ (torch.nonzero, cumsum with a leading 0, labels[sel]) bit for bit, in one launch.
+ *   txt_labels [n] int32, n = B*L: -1 = not masked, any other value a token id.
+ *   rows [cap] int32: rows[j] = the flat index of the j-th entry != -1, ascending (sel_idx of etp_mlm_fwd).
+ *   labels [cap] int64: labels[j] = that entry.
+ *   ptr_t [n+1] int32: ptr_t[i] = the number of selected entries below i (the transposed CSR pointer of etp_mlm_bwd).
+ *   status [2] int32: status[0] = 0 or the OR of ETP_MLM_ERR_COUNT (the count differs from n_expected) and ETP_MLM_ERR_LABEL (an
+ *     entry below -1 or >= vocab); status[1] = the count.
+ * n_expected is the count the caller sized the step for (the host knows it: mask_tokens runs there).  Whatever txt_labels holds,
+ * after the launch every rows[j], j < n_expected, lies in [0, n), every labels[j] in [0, vocab), ptr_t is non-decreasing with
+ * ptr_t[n] <= n_expected, and nothing at an index >= n_expected (<= cap) is written: a surplus entry is dropped, a short selection is
+ * filled with row 0 / label 0, a label is clamped, ptr_t is clamped to n_expected.  A flagged launch is numerically meaningless
+ * but no later kernel can take an out-of-range index from it.
+ * ETP_ERR_INVALID before anything is launched: a NULL pointer, n outside 1 .. 2^20, vocab < 1, n_expected outside 0 .. cap, an int32
+ * operand not 4-byte or labels not 8-byte aligned.
+ * One workgroup walks n in chunks of 256; wave ballots, every wave derives the prefix of the waves below it for itself.  Plain
+ * vector stores, no atomics, no LDS, no scratch; a second run gives the same bits. */
+#define ETP_MLM_ERR_COUNT 1
+#define ETP_MLM_ERR_LABEL 2
+int etp_mlm_select(const int32_t* txt_labels, int n, int vocab, int n_expected, int cap, int32_t* rows, int32_t* ptr_t,
+                   int64_t* labels, int32_t* status, etp_stream_t stream);
+
 /* Pre-training MLM task for a planner created with cfg.use_lang2visn = 1:
  * GlocalTextPathCMT.forward_mlm (pretrain vilmodel.py:708-754): the text (output of etp_txt_fwd) attends to the graph-node
  * inputs gmap_img_fts + step + position embeddings through forward_lang2visn of every x-layer (:400-411), then
