@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from ._lib import check, ptr
 from .planner import GlocalTextPathNavCMT
-from .step import INPUTS, N_MLM_INPUTS, _Staging, _destroy_streams, _new_stream
+from .step import N_MLM_INPUTS, _Staging, _destroy_streams, _new_stream
 
 MLM_ERR_COUNT, MLM_ERR_LABEL = 1, 2            # ETP_MLM_ERR_* of include/etpnav_hip.h
 
@@ -41,7 +41,7 @@ class MlmStep(_Staging):
             raise _lib.EtpError("the MLM task needs a model built with use_lang2visn_attn=True (pre-training config)")
         if select not in (None, "device", "host"):
             raise ValueError(f"select: None, 'device' or 'host' (got {select!r})")
-        self.select = "host" if select == "host" or os.environ.get("ETP_MLM_SELECT", "1") == "0" else "device"
+        self.select = self._planned_select = "host" if select == "host" or os.environ.get("ETP_MLM_SELECT", "1") == "0" else "device"
         self._stage(model, batch, N_MLM_INPUTS, dropout, drop_seed, 0.0, traj_nodes, capacity)
         # gradient accumulation (PretrainDriver): later micro-steps keep the arena (zero_grads False) and every micro-step's mean
         # loss is scaled by 1 / accumulation steps (train_r2r.py:250-252)
@@ -73,9 +73,12 @@ class MlmStep(_Staging):
                       "sel_status": ((2,), torch.int32)})
         return a
 
-    def _bind(self, batch, first: bool = False):
-        new = super()._bind(batch, first)
-        self.Nm = self._d["Nm"]
+    def _bind(self, batch, d):
+        """_Staging's, then the batch's selection, on the stream the step runs on"""
+        if self.select != self._planned_select:            # the route was switched on a live step: its arrays are another plan's
+            self._bound, self._planned_select = None, self.select
+        new = super()._bind(batch, d)
+        self.Nm = d["Nm"]
         self.dims = (self.B, self.Lt, self.Bp, self.V, self.G, self.eng.cconf.hidden)
         self._select(batch, new)
         return new
@@ -90,7 +93,7 @@ class MlmStep(_Staging):
         # arange and ones are written once per allocation, over all of it: the views of a later batch are prefixes
         for k, fill in (("_arange", lambda t: torch.arange(t.numel(), dtype=torch.int32, out=t)), ("_ones", lambda t: t.fill_(1.0))):
             if k in new:
-                fill(self._pool[k].view(getattr(self, k).dtype) if self._pool is not None else getattr(self, k))
+                fill(self._pool[k].view(getattr(self, k).dtype))
         if "sel_status" in new:
             self.sel_status.zero_()
         md = getattr(batch, "mlm_dev", None)
@@ -107,7 +110,7 @@ class MlmStep(_Staging):
         self._lab_src = lab                    # taken by reference until the next load, like traj_dev
         self.sel = (self._arange, self._rows, self._ones)
         self.selT = (self._ptr_t, self._arange[:Nm], self._ones)
-        cap = self._pool["_rows"].numel() // 4 if self._pool is not None else Nm
+        cap = self._pool["_rows"].numel() // 4
         check(self.L.etp_mlm_select(ptr(lab), n, self.eng.cconf.vocab, Nm, cap, ptr(self._rows), ptr(self._ptr_t), ptr(self.labels),
                                     ptr(self.sel_status), self.eng.stream()), "mlm_select")
 
@@ -123,19 +126,6 @@ class MlmStep(_Staging):
         self.selT = (ptr_t.to(dev), i32(torch.arange(Nm)), torch.ones(Nm, dtype=torch.float32, device=dev))
         self.labels = batch["txt_labels"].reshape(-1)[sel].to(torch.int64).contiguous().to(dev)
 
-    def load_batch(self, batch: Dict[str, torch.Tensor]):
-        """Refill the step with another batch and build its selection, on the stream the step runs on.  A step built without
-        `capacity` takes the SAME shapes only (the masked count included); one built with it takes any (_Staging._bind)."""
-        if self._pool is None and self.batch_shape_key(batch) != self.shape_key():
-            raise ValueError(f"batch shapes {self.batch_shape_key(batch)} differ from this step's {self.shape_key()}")
-        if self._pool is None:
-            for k, src, dt in INPUTS[:N_MLM_INPUTS]:
-                self.inp[k].copy_(batch[src].to(dt), non_blocking=True)
-            self._select(batch)
-        else:
-            self._bind(batch)
-        self._load_nodes(batch)
-
     def check_select(self) -> None:
         """one device-to-host copy of etp_mlm_select's status words; raises EtpError naming the flags, the count the kernel found and
         the count the step was sized for.  The step itself never synchronises; a step on the host route has nothing to check."""
@@ -146,15 +136,6 @@ class MlmStep(_Staging):
             names = [n for n, bit in (("ETP_MLM_ERR_COUNT", MLM_ERR_COUNT), ("ETP_MLM_ERR_LABEL", MLM_ERR_LABEL)) if flags & bit]
             raise _lib.EtpError(f"etp_mlm_select flagged {' | '.join(names)}: {count} entries of txt_labels are masked, the step was "
                                 f"sized for n_masked = {self.Nm} (vocabulary {self.eng.cconf.vocab})")
-
-    @staticmethod
-    def batch_shape_key(batch):
-        B, Lt = batch["txt_ids"].shape
-        Bp, V = batch["rgb_fts"].shape[:2]
-        return (B, Lt, Bp, V, batch["gmap_step_ids"].shape[1], int((batch["txt_labels"] != -1).sum()))
-
-    def shape_key(self):
-        return (self.B, self.Lt, self.Bp, self.V, self.G, self.Nm)
 
     def close(self):
         self.eng.release_aux()
@@ -303,9 +284,10 @@ class PretrainDriver:
     find_unused_parameters=True, utils/misc.py:58) -> warm-up-linear learning rate (optim/sched.py) -> fused AdamW with the
     reference's decay grouping and gradient clipping (optim/misc.py, optim/adamw.py, train_r2r.py:283-300).
 
-    Step objects (preallocated stash / workspace / streams) are cached per batch shape and refilled in place for SAP; the MLM
-    step is rebuilt per batch (its masked-token count changes the buffer plan).  With reuse_steps=True one capacity step object per
-    task serves the whole run instead (and one more pair validate()): load_batch of any shape, no synchronise per batch."""
+    _step_for picks the step object of every batch.  Fixed SAP steps (their own stash / workspace / streams) are cached per batch
+    shape, training and validation apart, and refilled in place; the MLM step is built per batch and released after it (its
+    masked-token count changes the buffer plan).  With reuse_steps=True one capacity step object per task serves the whole run
+    instead (and one more pair validate()): load_batch of any shape, no synchronise per batch."""
 
     def __init__(self, model: GlocalTextPathNavCMT, loaders: Dict, learning_rate: float = 5e-5, warmup_steps: int = 10000,
                  num_train_steps: int = 100000, grad_norm: float = 5.0, accum_steps: int = 1, dropout="config", seed: int = 0,
@@ -353,20 +335,40 @@ class PretrainDriver:
         self.lr_history = []
         self.val_logs = []                  # (global_step, dict) of every validation point of run()
 
-    def _reused_step(self, task: str, train: bool, batch):
-        """reuse_steps: the one step object of (task, training / validation), built at the first batch and refilled ever after"""
+    def _step_for(self, task: str, train: bool, batch):
+        """The step object that runs `batch`, loaded with it.  reuse_steps: the one capacity step of (task, training / validation), built
+        at the first batch and refilled ever after.  Otherwise SAP: the fixed step of the batch's shape from the training or the
+        validation cache (max_cached_steps each, the oldest evicted); MLM: a step of this batch alone, which the caller _release()s."""
         from .step import PlannerStep
-        st = self._reused.get((task, train))
-        if st is not None:
-            st.load_batch(batch)
-            return st
         kw = dict(dropout=self.dropout, drop_seed=self.seed) if train else dict(dropout=None)
-        if task == "sap":
-            st = PlannerStep(self.model, batch, zero_grads=train, grad_overwrite=False, capacity=self._capacity, **kw)
+        kw["capacity"] = self._capacity if self.reuse_steps else None
+
+        def make():
+            if task == "sap":
+                # accumulate-mode gradients + full zeroing: the pre-training variant carries weights this task does not touch
+                return PlannerStep(self.model, batch, zero_grads=train, grad_overwrite=False, **kw)
+            return MlmStep(self.model, batch, **kw)
+
+        if self.reuse_steps:
+            cache, key = self._reused, (task, train)
+        elif task == "sap":
+            cache, key = (self._sap if train else self._sap_eval), PlannerStep.batch_shape_key(batch)
         else:
-            st = MlmStep(self.model, batch, capacity=self._capacity, **kw)
-        self._reused[(task, train)] = st
+            return make()
+        st = cache.get(key)
+        if st is None:
+            if not self.reuse_steps and len(cache) >= self._max:
+                cache.pop(next(iter(cache))).close()
+            st = cache[key] = make()
+        else:
+            st.load_batch(batch)
         return st
+
+    def _release(self, st) -> None:
+        """done with a step of one batch alone (the MLM step without reuse_steps): its buffers must be idle before they go"""
+        if isinstance(st, MlmStep) and not self.reuse_steps:
+            torch.cuda.current_stream().synchronize()
+            st.close()
 
     def check_steps(self) -> None:
         """reuse_steps: what the reused steps' status words hold (check_select / check_traj): one small copy per step object"""
@@ -374,22 +376,6 @@ class PretrainDriver:
             st.check_traj()
             if isinstance(st, MlmStep):
                 st.check_select()
-
-    def _sap_step(self, batch):
-        from .step import PlannerStep
-        if self.reuse_steps:
-            return self._reused_step("sap", True, batch)
-        key = PlannerStep.batch_shape_key(batch)
-        st = self._sap.get(key)
-        if st is None:
-            if len(self._sap) >= self._max:
-                self._sap.pop(next(iter(self._sap))).close()
-            # accumulate-mode gradients + full zeroing: the pre-training variant carries weights this task does not touch
-            st = PlannerStep(self.model, batch, dropout=self.dropout, drop_seed=self.seed, zero_grads=True, grad_overwrite=False)
-            self._sap[key] = st
-        else:
-            st.load_batch(batch)
-        return st
 
     def train_step(self, name: str, batch) -> torch.Tensor:
         """One micro-step on `batch` of task `name` ('sap...' / 'mlm...': the part before '_' selects the task, as
@@ -400,7 +386,7 @@ class PretrainDriver:
         first = self._micro == 0
         A = self.accum_steps
         if task == "sap":
-            st = self._sap_step(batch)
+            st = self._step_for("sap", True, batch)
             st.step_no = self.global_step * A + self._micro
             st.zero_grads = first
             st.loss_scale = 1.0 / (st.B * A)
@@ -409,8 +395,7 @@ class PretrainDriver:
                 raise ValueError(f"instruction length {st.Lt} exceeds max_txt_len={self.max_txt_len} (the exchange capacity)")
             self._touched.append((st.inp["txt_ids"].reshape(-1).clone() if A > 1 else st.inp["txt_ids"].reshape(-1), st.B))
         elif task == "mlm":
-            st = self._reused_step("mlm", True, batch) if self.reuse_steps else \
-                MlmStep(self.model, batch, dropout=self.dropout, drop_seed=self.seed)
+            st = self._step_for("mlm", True, batch)
             st.step_no = self.global_step * A + self._micro
             st.zero_grads = first
             st.loss_scale = 1.0 / A
@@ -421,9 +406,7 @@ class PretrainDriver:
         self._micro += 1
         self.task_losses.setdefault(name, []).append(loss)
         if self._micro < A:
-            if task == "mlm" and not self.reuse_steps:
-                torch.cuda.current_stream().synchronize()
-                st.close()
+            self._release(st)
             return loss
         if self.distributed:
             red = self.reducers[task]
@@ -438,24 +421,8 @@ class PretrainDriver:
         self.global_step += 1
         self.lr_history.append(self.sched.step(self.global_step))
         self.opt.step()
-        if task == "mlm" and not self.reuse_steps:
-            torch.cuda.current_stream().synchronize()      # the per-batch MLM step object is released: its buffers must be idle
-            st.close()
+        self._release(st)
         return loss
-
-    def _sap_eval_step(self, batch):
-        from .step import PlannerStep
-        if self.reuse_steps:
-            return self._reused_step("sap", False, batch)
-        key = PlannerStep.batch_shape_key(batch)
-        st = self._sap_eval.get(key)
-        if st is None:
-            if len(self._sap_eval) >= self._max:
-                self._sap_eval.pop(next(iter(self._sap_eval))).close()
-            st = self._sap_eval[key] = PlannerStep(self.model, batch, dropout=None, zero_grads=False, grad_overwrite=False)
-        else:
-            st.load_batch(batch)
-        return st
 
     def validate(self, val_loaders: Dict, setname: str = "") -> Dict[str, float]:
         """validate() of train_r2r.py:335-444 (model.eval(): no dropout): for every task of `val_loaders` ({task: batches}) one
@@ -474,17 +441,13 @@ class PretrainDriver:
             counters.reset()
             t0 = time.time()
             for batch in loader:
+                st = self._step_for(task, False, batch)
                 if task == "sap":
-                    st = self._sap_eval_step(batch)
                     st.run_eager(backward=False)
                     sap_eval(st, counters)
-                elif self.reuse_steps:
-                    self._reused_step("mlm", False, batch).run_eval(counters)
                 else:
-                    st = MlmStep(self.model, batch, dropout=None)
                     st.run_eval(counters)
-                    torch.cuda.current_stream().synchronize()      # the per-batch MLM step object is released, as in train_step
-                    st.close()
+                self._release(st)
             loss_sum, n_correct, n_rows = sum_over_ranks(counters.read())
             dt = time.time() - t0
             keys = ("loss", "acc") if task == "mlm" else ("gloss", "gacc")

@@ -1,6 +1,6 @@
 """One whole planner training step (the unit of BASELINE.json's metric) driven straight through the C ABI.
 
-``PlannerStep`` preallocates every buffer for a fixed (B, L, V, G) shape and runs
+``PlannerStep`` keeps every buffer in allocations of its own (sized by its first batch, or grow-only with ``capacity``) and runs
 
     weight refresh (bf16) -> zero grads -> forward_txt -> forward_panorama -> node assembly (gather-mean)
     -> forward_navigation -> cross-entropy(sum)/B -> backward of all of it into the flat gradient arena
@@ -89,8 +89,8 @@ INPUTS = (("txt_ids", "txt_ids", torch.int64), ("txt_masks", "txt_masks", torch.
           ("gmask", "gmap_masks", torch.bool),
           ("visited", "gmap_visited_masks", torch.bool), ("dists", "gmap_pair_dists", torch.float32), ("labels", "labels", torch.int64))
 N_MLM_INPUTS = 10
-# the axes of every input in terms of a step's dimensions ('*' = a feature width, taken from the batch): what a capacity step sizes
-# its input allocations by
+# the axes of every input in terms of a step's dimensions ('*' = a feature width, taken from the batch): what a step sizes its input
+# allocations by and checks every batch against
 INPUT_AXES = {"txt_ids": "BL", "txt_masks": "BL", "rgb": "RV*", "dep": "RV*", "loc": "RV*", "nav": "RV", "view_lens": "R", "step_ids": "BG",
               "pos": "BG*", "gmask": "BG", "visited": "BG", "dists": "BGG", "labels": "B"}
 CAPACITY_KEYS = ("B", "L", "R", "V", "G", "Nm")
@@ -101,10 +101,12 @@ class _Staging:
     text and panorama branches, dropout state -- and the library calls both issue with the same arguments.  The two schedules
     themselves (which stream, which order) stay written out in each class.
 
-    A step built with ``capacity`` (a dict with any of B, L, R, V, G, Nm, or True = the first batch) keeps every one of these in an
-    allocation sized for the capacity; the step's tensors are contiguous views of the current batch's shape at offset 0 of them, and
-    ``load_batch`` accepts any shape: every entry point of the library recomputes its buffer plan from the dimensions it is called
-    with, so a buffer that is large enough serves any smaller shape.  ``regrows`` counts the loads that had to enlarge something."""
+    Every one of these lives in an allocation of the step's own (``_pool``: one byte buffer per name); the step's tensors are
+    contiguous views of the current batch's shape at offset 0 of them.  Without ``capacity`` the step is fixed: the allocations are
+    those of its first batch and ``load_batch`` refuses any other dimensions.  With ``capacity`` (a dict with any of B, L, R, V, G, Nm,
+    or True = the first batch) they are sized for the capacity and ``load_batch`` accepts any shape: every entry point of the library
+    recomputes its buffer plan from the dimensions it is called with, so a buffer that is large enough serves any smaller shape.
+    ``regrows`` counts the loads that had to enlarge something (a fixed step's stays 0)."""
 
     def _dims_of(self, batch) -> Dict[str, int]:
         B, L = batch["txt_ids"].shape
@@ -128,13 +130,13 @@ class _Staging:
         """name -> (shape, dtype) of the integer arrays the step owns"""
         return {"traj_status": ((d["B"] * d["G"] + d["R"],), torch.int32)} if self.traj_nodes else {}
 
+    def _input_shape(self, k, t, d):
+        """the shape the dimensions d give the staged input k, feature widths from the batch's tensor t"""
+        return tuple(d[a] if a != "*" else int(t.shape[n]) for n, a in enumerate(INPUT_AXES[k]))
+
     def _plan(self, d, batch):
         """name -> (bytes, shape, dtype) of everything the step allocates at the dimensions d; shape None = a byte buffer"""
-        plan = {}
-        for k, src, dt in INPUTS[:self._n_inputs] if self._pool is not None else ():
-            t = batch[src]
-            shape = tuple(d[a] if a != "*" else int(t.shape[n]) for n, a in enumerate(INPUT_AXES[k]))
-            plan["in:" + k] = (shape, dt)
+        plan = {"in:" + k: (self._input_shape(k, batch[src], d), dt) for k, src, dt in INPUTS[:self._n_inputs]}
         plan.update({k: (s, torch.bool if k == "pmask" else torch.float32) for k, s in self._api_tensors(d).items()})
         plan.update(self._int_arrays(d))
         out = {}
@@ -149,37 +151,29 @@ class _Staging:
             out[k] = (int(nbytes), None, None)
         return out
 
-    def _bind(self, batch, first: bool = False):
-        """(re)point the step's tensors at `batch`'s dimensions.  A capacity step views its allocations, enlarging (never shrinking)
-        whatever the library's byte queries for the new dimensions find short -- one device synchronise per such load, since the
-        side streams of the step that last used the old allocation are not torch's.  -> the names whose allocation is new."""
-        d = self._d = self._dims_of(batch)
-        for k, src, _ in INPUTS[:self._n_inputs] if self._pool is not None else ():
-            want = tuple(d[a] if a != "*" else int(batch[src].shape[n]) for n, a in enumerate(INPUT_AXES[k]))
-            if tuple(batch[src].shape) != want:
-                raise ValueError(f"batch[{src!r}] has shape {tuple(batch[src].shape)}, the batch's dimensions {d} make it {want}")
-        self.B, self.Lt, self.Bp, self.V, self.G = d["B"], d["L"], d["R"], d["V"], d["G"]
-        need = self._plan(d, batch)
-        dev, new = self.eng.device, []
-        if self._pool is None:                 # today's exact allocations
-            for k, (nbytes, shape, dt) in need.items():
-                if k.startswith("in:"):
-                    continue
-                setattr(self, k, self.eng.buf(nbytes) if shape is None else torch.empty(shape, dtype=dt, device=dev))
-                new.append(k)
-            self.inp = {k: batch[src].to(dt).contiguous().to(dev) for k, src, dt in INPUTS[:self._n_inputs]}
-        else:
+    def _bind(self, batch, d):
+        """(re)point the step's tensors at `batch`, whose dimensions are d, and copy its inputs in: views of the step's allocations,
+        enlarging (never shrinking) whatever the library's byte queries for d find short -- one device synchronise per load that does
+        so after the first, since the side streams of the step that last used the old allocation are not torch's.  A batch of the very
+        shape that is bound only has its inputs checked and copied (tools/step_load_bench.py); a fixed step only comes here with the
+        dimensions it was built for, so that is its every load.  -> the names whose allocation is new."""
+        inputs = INPUTS[:self._n_inputs]
+        shapes = {k: self._input_shape(k, batch[src], d) for k, src, _ in inputs}
+        for k, src, _ in inputs:
+            if tuple(batch[src].shape) != shapes[k]:
+                raise ValueError(f"batch[{src!r}] has shape {tuple(batch[src].shape)}, the batch's dimensions {d} make it {shapes[k]}")
+        short = []
+        if (d, shapes) != self._bound:         # else the shape that is bound already (every load of a fixed step): plan and views stand
+            need = self._plan(d, batch)
             short = [k for k, (nbytes, _, _) in need.items() if k not in self._pool or self._pool[k].numel() < nbytes]
             if short:
                 self._cap = {k: max(self._cap.get(k, 0), v) for k, v in d.items()}
                 at_cap = self._plan(self._cap, batch)
-                if not first:
-                    torch.cuda.synchronize(dev)
+                if self._pool:                 # not the step's first batch
+                    torch.cuda.synchronize(self.eng.device)
                     self.regrows += 1
                 for k in short:
                     self._pool[k] = self.eng.buf(max(need[k][0], at_cap[k][0], 1))
-                new = short
-            self.inp = getattr(self, "inp", None) or {}
             for k, (nbytes, shape, dt) in need.items():
                 t = self._pool[k][:nbytes]
                 if shape is not None:
@@ -188,11 +182,31 @@ class _Staging:
                     self.inp[k[3:]] = t
                 else:
                     setattr(self, k, t)
-            for k, src, dt in INPUTS[:self._n_inputs]:
-                self.inp[k].copy_(batch[src].to(dt), non_blocking=True)
+            self._bound, self._d = (d, shapes), d
+            self.B, self.Lt, self.Bp, self.V, self.G = d["B"], d["L"], d["R"], d["V"], d["G"]
+        for k, src, dt in inputs:
+            self.inp[k].copy_(batch[src].to(dt), non_blocking=True)
         if self.traj_nodes:                    # forward [B*G] node rows, backward [Bp] steps; a forward-only step leaves the latter alone
             self.traj_status.zero_()
-        return new
+        return short
+
+    def shape_key(self):
+        return tuple(self._d.values())
+
+    def load_batch(self, batch: Dict[str, torch.Tensor]):
+        """Refill the step with another batch: the inputs are copied into the step's own allocations (the stash / workspace buffers and
+        the streams are reused; only the small CSR index arrays of the node aggregation are rebuilt, or, on the table route, the new
+        batch's descriptor tensors are taken by reference).  A fixed step takes the dimensions it was built for only (for MlmStep the
+        masked count included); a step built with `capacity` takes any: its tensors are re-viewed at the new dimensions and whatever
+        is short grows (_bind)."""
+        d = self._dims_of(batch)
+        if self._fixed and d != self._d:
+            raise ValueError(f"batch shapes {tuple(d.values())} differ from this step's {self.shape_key()}")
+        if self.graphs:
+            # the CSR index tensors (the descriptor tensors) below are new allocations: kernel nodes of an existing graph would keep the old pointers
+            raise RuntimeError("load_batch() on a step with captured / recorded graphs: close() the graphs (or build a new step) first")
+        self._bind(batch, d)
+        self._load_nodes(batch)
 
     def _stage(self, model: GlocalTextPathNavCMT, batch, n_inputs: int, dropout, drop_seed: int, p_env: float,
                traj_nodes: Optional[bool] = None, capacity=None):
@@ -204,13 +218,13 @@ class _Staging:
             dropout = config_dropout_rates(model.config) + (float(p_env),)
         self.dropout, self.drop_seed, self.step_no = dropout, int(drop_seed) & 0xFFFFFFFF, 0
         self._n_inputs, self.regrows = n_inputs, 0
-        if capacity is None or capacity is False:
-            self._pool = self._cap = None
-        else:
-            cap = {} if capacity is True else dict(capacity)
-            if any(k not in CAPACITY_KEYS for k in cap):
-                raise ValueError(f"capacity: a dict with any of {CAPACITY_KEYS} or True (got {sorted(cap)})")
-            self._pool, self._cap = {}, {k: int(v) for k, v in cap.items()}
+        self._fixed = capacity is None or capacity is False        # its capacity is its first batch
+        cap = {} if self._fixed or capacity is True else dict(capacity)
+        if any(k not in CAPACITY_KEYS for k in cap):
+            raise ValueError(f"capacity: a dict with any of {CAPACITY_KEYS} or True (got {sorted(cap)})")
+        self._pool, self._cap, self.inp = {}, {k: int(v) for k, v in cap.items()}, {}
+        self._bound = self._d = None           # (dimensions, input shapes) the step's tensors are views of; the dimensions alone
+        self.graphs = []                       # PlannerStep's captured / recorded graphs: load_batch refuses while there are any
         # node features of a trajectory batch straight from its integer tables (etp_traj_nodes_fwd / _bwd, csrc/traj_batch.hip): whenever
         # the batch carries them (TrajBatch.traj_dev of the native loaders), or forced for a string-only batch; ETP_TRAJ_NODES=0 (read
         # once, here) or traj_nodes=False keep the host-built CSR + etp_gather_sum
@@ -218,7 +232,7 @@ class _Staging:
             (getattr(batch, "traj_dev", None) is not None or bool(traj_nodes))
         self.traj_dev = self.csr_f = self.csr_b = None
         self.loss = torch.zeros(1, dtype=torch.float32, device=eng.device)
-        self._bind(batch, first=True)
+        self._bind(batch, self._dims_of(batch))
         self._load_nodes(batch)
 
     def _drop_state(self):
@@ -317,8 +331,8 @@ class PlannerStep(_Staging):
         traj_nodes: None = the node features come from the batch's descriptor tables when it carries them (a loader's TrajBatch), else
         from the host-built CSR; True forces the tables for a string-only batch['traj'] (graph_inputs.traj_descriptors); False or
         ETP_TRAJ_NODES=0 keep the CSR.  check_traj() reads what the table route flagged.
-        capacity: None = buffers of exactly this batch's shape and a same-shape load_batch; a dict with any of B, L, R, V, G, or True
-        (this batch), = one step object for batches of any shape (_Staging)."""
+        capacity: None = a fixed step, allocations of this batch's dimensions and a load_batch of those dimensions only; a dict with any of
+        B, L, R, V, G, or True (this batch), = one step object for batches of any shape (_Staging)."""
         self.refresh_weights, self.zero_grads = refresh_weights, zero_grads
         # frozen sub-models (vlnbert_init.py:51-54 -> vilmodel_cmt.py:422-433,675-682): with fix_lang_embedding the text encoder's
         # output is detached (LanguageEncoder.forward :431-432) -- no text backward runs and no gradient reaches `embeddings.*` /
@@ -365,7 +379,6 @@ class PlannerStep(_Staging):
             pass                               # the bridges' join_aux sees this step's streams from now on
         self._pano_pending = False
         self.graph = None
-        self.graphs = []
         self.stream = None
 
     def _api_tensors(self, d):
@@ -381,8 +394,7 @@ class PlannerStep(_Staging):
 
     def _int_arrays(self, d):
         a = super()._int_arrays(d)
-        if self._pool is not None:             # validate.sap_eval's per-row outputs (it allocates them itself for a fixed-shape step)
-            a.update({"row_nll": ((d["B"],), torch.float32), "row_pred": ((d["B"],), torch.int32)})
+        a.update({"row_nll": ((d["B"],), torch.float32), "row_pred": ((d["B"],), torch.int32)})    # validate.sap_eval's per-row outputs
         return a
 
     def _scope(self, lazy: Optional[int] = None):
@@ -393,35 +405,17 @@ class PlannerStep(_Staging):
         return self.eng.scope(aux=self.aux, aux2=self.aux2, lazy=self._lazy if lazy is None else lazy, drop=self._drop_state(),
                               grad_overwrite=self.grad_overwrite)
 
-    def shape_key(self):
-        return (self.B, self.Lt, self.Bp, self.V, self.G)
-
     @staticmethod
     def batch_shape_key(batch):
+        """shape_key() of a step built for `batch`: what PretrainDriver's per-shape cache is keyed by"""
         B, Lt = batch["txt_ids"].shape
         Bp, V = batch["rgb_fts"].shape[:2]
         return (B, Lt, Bp, V, batch["gmap_step_ids"].shape[1])
 
     def load_batch(self, batch: Dict[str, torch.Tensor]):
-        """Refill the preallocated device inputs with another batch of the SAME shapes (the stash / workspace buffers and the
-        streams are reused; only the small CSR index arrays of the node aggregation are rebuilt, or, on the table route, the new
-        batch's descriptor tensors are taken by reference).  A step built with `capacity` takes a batch of any shape (_Staging._bind):
-        its tensors are re-viewed at the new dimensions and whatever is short grows."""
-        if self._pool is not None:
-            if self.graphs:
-                raise RuntimeError("load_batch() on a step with captured / recorded graphs: close() the graphs (or build a new step) first")
-            self._bind(batch)
-            self._load_nodes(batch)
-            self.loss_scale = 1.0 / self.B     # as a step built for this batch has it; a caller's own scale is set after the load
-            return
-        if self.batch_shape_key(batch) != self.shape_key():
-            raise ValueError(f"batch shapes {self.batch_shape_key(batch)} differ from this step's {self.shape_key()}")
-        if self.graphs:
-            # the CSR index tensors (the descriptor tensors) below are new allocations: kernel nodes of an existing graph would keep the old pointers
-            raise RuntimeError("load_batch() on a step with captured / recorded graphs: close() the graphs (or build a new step) first")
-        for k, src, dt in INPUTS:
-            self.inp[k].copy_(batch[src].to(dt), non_blocking=True)
-        self._load_nodes(batch)
+        super().load_batch(batch)
+        if not self._fixed:                    # as a step built for this batch has it; a caller's own scale is set after the load
+            self.loss_scale = 1.0 / self.B
 
     # ------------------------------------------------------------------------------------------
     def _enqueue_pano_bwd(self, s: int):

@@ -49,9 +49,6 @@ def sap_eval(step, counters: EvalCounters, stream=None) -> None:
     """The statements of validate_sap's loop body (train_r2r.py:424-430) on a PlannerStep whose forward has been enqueued
     (``run_eager(backward=False)``): per-row nll / arg-max of ``step.logits`` against the batch's labels, added to `counters`."""
     L, s = step.L, stream if stream is not None else step.eng.stream()
-    if getattr(step, "row_nll", None) is None:
-        step.row_nll = torch.empty(step.B, dtype=torch.float32, device=step.eng.device)
-        step.row_pred = torch.empty(step.B, dtype=torch.int32, device=step.eng.device)
     labels = step.inp["labels"]
     check(L.etp_sap_eval(ptr(step.logits), ptr(labels), step.B, step.G, SAP_IGNORE, ptr(step.row_nll), ptr(step.row_pred), s),
           "sap_eval")

@@ -4,11 +4,13 @@ One capacity PlannerStep and one capacity MlmStep run a sequence of six batches 
 one load that has to grow synchronises by itself).  Along the sequence every one of B, L, R, V, G, Nm shrinks and grows; B = 1 occurs
 once, batch 2 equals the capacity exactly, batch 4 exceeds it (regrows == 1).  Before each load the stashes, workspaces and API tensors
 -- values only, COVERAGE.md's schedule matrix -- are overwritten with 0xFF bytes, so a stale read shows as NaN.  Each batch is compared
-with a fresh step built for that batch alone (today's route), same dropout seed and step_no, eval and dropout modes, fp32 and bf16:
+with a fresh fixed step built for that batch alone, same dropout seed and step_no, eval and dropout modes, fp32 and bf16:
 forward tensors bit for bit, loss and every parameter gradient within the tolerance tests/test_sched_gpu.py uses for "same kernels,
 other order of atomics" (|got - ref| <= tol * max(1, max|ref|), tol 1e-4 fp32 / 2e-3 bf16, loss 1e-5; all-zero stays all-zero).
 That every side stream is joined when run_eager returns -- what the sync-free reuse rests on -- is test_sched_gpu.py's "ends joined"
-check and is not shown again here."""
+check and is not shown again here.  A fixed step (no capacity) is the same route with its first batch as its capacity: it reloads a batch
+of its dimensions in place with every pointer kept, refuses one more masked token and inputs that disagree with the batch's dimensions,
+and carries the rows validate.sap_eval writes."""
 import pytest
 import torch
 
@@ -25,24 +27,27 @@ SEQ = ((3, 19, 3, 9, 4, 11, 101), (1, 11, 2, 7, 3, 12, 102), (4, 24, 3, 11, 4, 1
 CAP_AT, GROWS_AT = 2, 4
 
 
+def _batch(cfg, B, L, T, V, nc, bseed, mseed, pick=None):
+    """one batch of the sequence; `pick`: the masked positions (default: drawn from mseed among the batch's own tokens)"""
+    from etpnav_amd.synthetic import make_sap_batch
+    b = make_sap_batch(cfg.vocab_size, cfg.image_feat_size, cfg.depth_feat_size, B, L, T, V, n_cand=nc, seed=bseed, ragged=True)
+    lab = torch.full_like(b["txt_ids"], -1)
+    if pick is None:
+        g = torch.Generator().manual_seed(mseed)
+        pick = (torch.rand(lab.shape, generator=g) < 0.25) & b["txt_masks"]
+        pick[:, 1] = True
+    lab[pick] = b["txt_ids"][pick]
+    ids = b["txt_ids"].clone()
+    ids[pick] = 103
+    b["txt_ids"], b["txt_labels"] = ids, lab
+    return b
+
+
 @pytest.fixture(scope="module")
 def case():
     from oracle.make_golden_pretrain import make_case
-    from etpnav_amd.synthetic import make_sap_batch
     cfg, P, _ = make_case()
-    batches = []
-    for B, L, T, V, nc, bseed, mseed in SEQ:
-        b = make_sap_batch(cfg.vocab_size, cfg.image_feat_size, cfg.depth_feat_size, B, L, T, V, n_cand=nc, seed=bseed, ragged=True)
-        g = torch.Generator().manual_seed(mseed)
-        lab = torch.full_like(b["txt_ids"], -1)
-        pick = (torch.rand(lab.shape, generator=g) < 0.25) & b["txt_masks"]
-        pick[:, 1] = True
-        lab[pick] = b["txt_ids"][pick]
-        ids = b["txt_ids"].clone()
-        ids[pick] = 103
-        b["txt_ids"], b["txt_labels"] = ids, lab
-        batches.append(b)
-    return cfg, P, batches
+    return cfg, P, [_batch(cfg, *spec) for spec in SEQ]
 
 
 def dims(b):
@@ -106,7 +111,6 @@ def test_one_capacity_step_runs_the_sequence(case, task, dtype, dropout):
     bit-identical.  The clause is kept as it was set."""
     cfg, P, batches = case
     model = _model(cfg, P, dtype)
-    tol = 1e-4 if dtype == torch.float32 else 2e-3
     refs = []
     for k, b in enumerate(batches):                      # today's route: a step object per batch
         st = _make(task, model, b, dropout)
@@ -136,6 +140,14 @@ def test_one_capacity_step_runs_the_sequence(case, task, dtype, dropout):
     finally:
         torch.cuda.synchronize()
         step.close()
+    failures = _differences(task, dtype, model, got, refs)
+    assert not failures, "\n".join(failures[:20])
+
+
+def _differences(task, dtype, model, got, refs):
+    """every snapshot of `got` against the fresh step's of `refs`: forward tensors bit for bit, loss and gradients within the file's
+    tolerances -> the failures"""
+    tol = 1e-4 if dtype == torch.float32 else 2e-3
     names = grad_slices(model)
     eng = model._engine
     offs = {n: (t.data_ptr() - eng.grads.data_ptr()) // 4 for n, t in names.items()}
@@ -157,7 +169,107 @@ def test_one_capacity_step_runs_the_sequence(case, task, dtype, dropout):
             if bad:
                 failures.append(f"batch {k}: {bad}")
         print(f"{task} {dtype} batch {k}: worst gradient |err| / tolerance {worst:.3g}")
+    return failures
+
+
+def _ptrs(step):
+    """data_ptr() of every input, API tensor, stash and workspace of the step"""
+    out = {"in:" + k: t.data_ptr() for k, t in step.inp.items()}
+    out.update({k: getattr(step, k).data_ptr() for k in list(step._api_tensors(step._d)) + list(step._byte_buffers(step._d))})
+    return out
+
+
+@pytest.mark.parametrize("task", ["sap", "mlm"])
+def test_a_fixed_step_reloads_a_batch_of_its_shape_in_place(case, task):
+    """A fixed step (no capacity) run on batch 0, then loaded with a second batch of the same dimensions -- other seeds for every tensor,
+    the masked positions of batch 0, so Nm is equal -- against a fresh step built for that second batch: the comparison and the
+    tolerances of test_one_capacity_step_runs_the_sequence (its docstring's intermittent clause on task = sap included)."""
+    cfg, P, batches = case
+    dtype, dropout = torch.float32, "config"
+    second = _batch(cfg, *SEQ[0][:5], 21, None, pick=batches[0]["txt_labels"] != -1)
+    assert dims(second) == dims(batches[0]) and not torch.equal(second["rgb_fts"], batches[0]["rgb_fts"])
+    model = _model(cfg, P, dtype)
+    fresh = _make(task, model, second, dropout)
+    fresh.step_no = 8
+    fresh.run_eager()
+    torch.cuda.synchronize()
+    ref = _snap(task, fresh, model)
+    fresh.close()
+    step = _make(task, model, batches[0], dropout)
+    try:
+        assert step._fixed and step.regrows == 0
+        step.step_no = 7
+        step.run_eager()
+        before = _ptrs(step)
+        assert {"in:rgb", "in:txt_ids", "txt", "pano", "gimg", "st_txt", "ws_txt", "st_pano", "ws_pano"} <= set(before)
+        _poison(step)
+        step.load_batch(second)                          # accepted
+        assert step.regrows == 0 and _ptrs(step) == before
+        step.step_no = 8
+        step.run_eager()
+        got = _snap(task, step, model)
+        torch.cuda.synchronize()
+        if task == "mlm":
+            step.check_select()
+        step.check_traj()
+    finally:
+        torch.cuda.synchronize()
+        step.close()
+    failures = _differences(task, dtype, model, [got], [ref])
     assert not failures, "\n".join(failures[:20])
+
+
+def test_a_fixed_step_refuses_what_it_was_not_built_for(case):
+    cfg, P, batches = case
+    model = _model(cfg, P, torch.float32)
+    b = batches[0]
+    more = dict(b)
+    free = torch.nonzero((b["txt_labels"] == -1) & b["txt_masks"])[0]
+    more["txt_labels"] = b["txt_labels"].clone()
+    more["txt_labels"][free[0], free[1]] = b["txt_ids"][free[0], free[1]]
+    assert {k: v for k, v in dims(more).items() if k != "Nm"} == {k: v for k, v in dims(b).items() if k != "Nm"}
+    assert dims(more)["Nm"] == dims(b)["Nm"] + 1
+    mlm = pretrain.MlmStep(model, b)
+    try:
+        with pytest.raises(ValueError, match="differ from this step's"):
+            mlm.load_batch(more)                         # the same (B, L, R, V, G), one more masked token
+    finally:
+        mlm.close()
+    short = dict(b)
+    short["dep_fts"] = b["dep_fts"][:, :-1]              # one view fewer than rgb_fts
+    with pytest.raises(ValueError, match=r"batch\['dep_fts'\] has shape .* the batch's dimensions"):
+        step_mod.PlannerStep(model, short)
+    sap = step_mod.PlannerStep(model, b)
+    try:
+        with pytest.raises(ValueError, match=r"batch\['dep_fts'\] has shape .* the batch's dimensions"):
+            sap.load_batch(short)
+    finally:
+        torch.cuda.synchronize()
+        sap.close()
+
+
+def test_sap_eval_writes_into_the_rows_a_fixed_step_planned(case):
+    from etpnav_amd.validate import EvalCounters, sap_eval
+    cfg, P, batches = case
+    model = _model(cfg, P, torch.float32)
+    step = step_mod.PlannerStep(model, batches[0], dropout=None, zero_grads=False, grad_overwrite=False)
+    try:
+        B = batches[0]["txt_ids"].shape[0]
+        assert step._fixed and tuple(step.row_nll.shape) == tuple(step.row_pred.shape) == (B,)
+        assert step.row_nll.dtype == torch.float32 and step.row_pred.dtype == torch.int32
+        at = (step.row_nll.data_ptr(), step.row_pred.data_ptr())
+        assert at == (step._pool["row_nll"].data_ptr(), step._pool["row_pred"].data_ptr())
+        counters = EvalCounters(DEV)
+        for _ in range(2):
+            step.run_eager(backward=False)
+            sap_eval(step, counters)
+            assert (step.row_nll.data_ptr(), step.row_pred.data_ptr()) == at
+        torch.cuda.synchronize()
+        loss_sum, _, n_rows = counters.read()
+        assert n_rows == 2 * B and abs(loss_sum - 2.0 * float(step.row_nll.double().sum())) <= 1e-4 * abs(loss_sum)   # the rows were written
+    finally:
+        torch.cuda.synchronize()
+        step.close()
 
 
 def test_kernel_route_and_host_route_build_the_same_selection(case):

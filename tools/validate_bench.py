@@ -128,7 +128,7 @@ def validate_legs(n_batches):
         out["val_mlm_loss"], out["val_mlm_acc"] = loss / rows, correct / rows
         loss, correct, rows = 0.0, 0, 0
         for b in batches:
-            st = drv._sap_eval_step(b)
+            st = drv._step_for("sap", False, b)
             st.run_eager(backward=False)
             labels = st.inp["labels"]
             loss += F.cross_entropy(st.logits, labels, reduction="sum").data.item()
