@@ -649,6 +649,23 @@ int etp_eval_accum(const float* row_nll, const int32_t* row_pred, const int64_t*
                    etp_eval_record* acc, etp_stream_t s) {
   return eval_accum(row_nll, row_pred, labels, n, (long)ignore_index, acc, (hipStream_t)s);
 }
+int etp_train_meter_loss(const float* loss, double smooth, const uint8_t* txt_masks, int64_t n_mask_bytes, int64_t n_examples,
+                         int64_t n_loss_units, etp_train_task_record* rec, etp_stream_t s) {
+  return train_meter_loss(loss, smooth, txt_masks, (long)n_mask_bytes, (long)n_examples, (long)n_loss_units, rec, (hipStream_t)s);
+}
+int etp_train_meter_step(const float* sumsq, const int32_t* nonfinite, etp_train_step_record* rec, etp_stream_t s) {
+  return train_meter_step(sumsq, nonfinite, rec, (hipStream_t)s);
+}
+int etp_tensor_report_create(const int64_t* seg_off, const int64_t* seg_len, const uint8_t* include, int n_seg, int64_t arena_len,
+                             etp_tensor_report_plan** plan) {
+  return tensor_report_create(seg_off, seg_len, include, n_seg, (long)arena_len, plan);
+}
+int64_t etp_tensor_report_chunks(const etp_tensor_report_plan* plan) { return tensor_report_chunks(plan); }
+int etp_tensor_report(etp_tensor_report_plan* plan, const float* arena, etp_tensor_record* records_out, float* sumsq_out,
+                      int32_t* nonfinite_out, etp_stream_t s) {
+  return tensor_report(plan, arena, records_out, sumsq_out, nonfinite_out, (hipStream_t)s);
+}
+int etp_tensor_report_destroy(etp_tensor_report_plan* plan) { return tensor_report_destroy(plan); }
 int etp_gelu_bwd(int dtype, void* d, const void* z, int64_t n, etp_stream_t s) {
   ETP_REQUIRE(dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
   ETP_REQUIRE(d && z && n >= 0, "null pointer / negative count");

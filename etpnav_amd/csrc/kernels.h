@@ -72,6 +72,16 @@ int sap_eval(const float* logits, const int64_t* labels, int B, int G, long igno
              hipStream_t st);
 int eval_accum(const float* row_nll, const int32_t* row_pred, const int64_t* labels, int n, long ignore_index, etp_eval_record* acc,
                hipStream_t st);
+// trainlog.hip: the training log's device records (running losses, gradient norm) and the per-tensor report of a float arena
+int train_meter_loss(const float* loss, double smooth, const uint8_t* txt_masks, long n_mask_bytes, long n_examples, long n_loss_units,
+                     etp_train_task_record* rec, hipStream_t st);
+int train_meter_step(const float* sumsq, const int32_t* nonfinite, etp_train_step_record* rec, hipStream_t st);
+int tensor_report_create(const int64_t* seg_off, const int64_t* seg_len, const uint8_t* include, int n_seg, long arena_len,
+                         etp_tensor_report_plan** out);
+long tensor_report_chunks(const etp_tensor_report_plan* p);
+int tensor_report(etp_tensor_report_plan* p, const float* arena, etp_tensor_record* records_out, float* sumsq_out,
+                  int32_t* nonfinite_out, hipStream_t st);
+int tensor_report_destroy(etp_tensor_report_plan* p);
 int zero_f32(float* dst, long n, hipStream_t st);
 int repeat_block(const void* src, void* dst, long bytes, int T, hipStream_t st);            // dst[t][.] = src[.], t < T
 int sum_steps(int dtype, const void* src, void* dst, long n, int steps, hipStream_t st);   // dst[i] = sum_t src[t][i], fp32 accumulation

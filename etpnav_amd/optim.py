@@ -27,10 +27,17 @@ NO_DECAY_SUBSTRINGS = ("bias", "LayerNorm.bias", "LayerNorm.weight")      # opti
 class FusedAdamW:
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  hf_style: bool = False, correct_bias: bool = True, max_grad_norm: float = 0.0,
-                 no_decay: Optional[Callable[[str], bool]] = None, check_finite: bool = False):
+                 no_decay: Optional[Callable[[str], bool]] = None, check_finite: bool = False, norm_route: str = "atomic"):
         """Defaults = torch.optim.AdamW's (the fine-tuning optimizer).  For the pre-training optimizer use
         ``hf_style=True, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, max_grad_norm=5.0,
-        no_decay=FusedAdamW.reference_no_decay``.  `no_decay(name) -> bool` selects parameters WITHOUT weight decay."""
+        no_decay=FusedAdamW.reference_no_decay``.  `no_decay(name) -> bool` selects parameters WITHOUT weight decay.
+        norm_route: how the squared gradient norm and the non-finite count are formed -- "atomic": etp_grad_sqnorm (one float atomic
+        per workgroup: the last bits differ from run to run); "report": etp_tensor_report over the gradient arena (etpnav_amd.trainlog:
+        per tensor, in double, in a fixed order, frozen parameters left out; the same bits every run, and ``grad_report()`` names
+        the tensor that went wrong)."""
+        if norm_route not in ("atomic", "report"):
+            raise ValueError(f"norm_route: 'atomic' or 'report' (got {norm_route!r})")
+        self.norm_route = norm_route
         self.model = model
         eng = self.eng = model._engine
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
@@ -54,6 +61,11 @@ class FusedAdamW:
         self._build_mask()
         if no_decay is not None:
             self.set_no_decay_names([name for name, _, _ in eng.table if no_decay(name)])
+        self._report = None
+        if norm_route == "report":
+            from .trainlog import TensorReport
+            fz = set(self.frozen_names)
+            self._report = TensorReport(eng.table, eng.total, dev, include=[name for name, _, _ in eng.table if name not in fz])
 
     def set_no_decay_names(self, names):
         """Exclude exactly these parameters from weight decay (one mask byte per 64 elements; every parameter starts on a
@@ -81,6 +93,9 @@ class FusedAdamW:
 
     def _sqnorm(self, s):
         eng = self.eng
+        if self._report is not None:           # the totals are stored, not accumulated: nothing to zero
+            self._report.run(eng.grads, s, sumsq=self.sumsq, nonfinite=self.nonfinite)
+            return
         self.sumsq.zero_(); self.nonfinite.zero_()
         if self.frozen_names:
             check(eng.L.etp_grad_sqnorm_masked(ptr(eng.grads), eng.total, ptr(self.decay_mask), ptr(self.sumsq), ptr(self.nonfinite), s),
@@ -113,6 +128,18 @@ class FusedAdamW:
         """Global L2 norm of the (still scaled) gradients, as a device scalar."""
         self._sqnorm(self.eng.stream())
         return self.sumsq.sqrt()
+
+    def grad_report(self):
+        """norm_route="report": {name: (sum, absmax, l2, nonfinite)} of every gradient tensor as the last norm pass saw it (one
+        device-to-host copy); ``first_nonfinite()`` of the same records names the first tensor holding a NaN or an inf"""
+        if self._report is None:
+            raise _lib.EtpError('grad_report() needs FusedAdamW(norm_route="report")')
+        return self._report.read()
+
+    def first_nonfinite(self):
+        if self._report is None:
+            raise _lib.EtpError('first_nonfinite() needs FusedAdamW(norm_route="report")')
+        return self._report.first_nonfinite()
 
     def step(self, grad_scale: float = 1.0, zero_grads: bool = True):
         """grad_scale multiplies the raw gradients (1/loss_scale for a GradScaler, 1/world_size after a summed

@@ -292,7 +292,7 @@ class PretrainDriver:
     def __init__(self, model: GlocalTextPathNavCMT, loaders: Dict, learning_rate: float = 5e-5, warmup_steps: int = 10000,
                  num_train_steps: int = 100000, grad_norm: float = 5.0, accum_steps: int = 1, dropout="config", seed: int = 0,
                  distributed: bool = False, max_cached_steps: int = 4, generator=None, max_txt_len: int = 100,
-                 reuse_steps: bool = False, batch_size: Optional[int] = None):
+                 reuse_steps: bool = False, batch_size: Optional[int] = None, log_steps: Optional[int] = None, on_log=None):
         """accum_steps = gradient_accumulation_steps of train_r2r.py:231-300: that many consecutive (task, batch) draws (the
         MetaLoader keeps the task fixed over them, loader.py:61-63) each add the gradient of mean-loss / accum_steps to the
         arena, then ONE reduction / clipping / optimizer step follows.  max_txt_len = the dataset's truncation length
@@ -301,7 +301,13 @@ class PretrainDriver:
         reuse_steps: one capacity PlannerStep and one capacity MlmStep serve training for the whole run and one more pair serves
         validate() (step.py _Staging: load_batch of any shape), instead of the per-shape cache and the per-batch MlmStep; the initial
         capacity is B = batch_size (default: the loaders' ``batch_size`` attribute, else the first batch) and L = max_txt_len, the rest
-        grows on demand.  Nothing synchronises per batch; check_select() / check_traj() run at the validation points and in close()."""
+        grows on demand.  Nothing synchronises per batch; check_select() / check_traj() run at the validation points and in close().
+        log_steps: the training log of train_r2r.py:259-317 on the device (etpnav_amd.trainlog.TrainMeter): every micro-step's loss goes
+        into its task's running meter and counters instead of ``task_losses``, every optimizer step's pre-clip gradient norm into the
+        step record, and after every log_steps-th optimizer step ONE read -- the only host synchronise of the training route --
+        gives the reference's scalars (``loss/{task}``, ``grad_norm``, ``perf/{task}_*_per_s``, plus ``lr`` from the schedule and the
+        skip / non-finite counts), appended to ``train_logs`` as (global_step, dict) and handed to on_log(global_step, dict).  None:
+        no meter, ``task_losses`` grows by one device scalar per micro-step as before."""
         from .optim import FusedAdamW, WarmupLinearLR
         from . import dp
         if accum_steps < 1:
@@ -334,6 +340,14 @@ class PretrainDriver:
         self.task_losses = {}
         self.lr_history = []
         self.val_logs = []                  # (global_step, dict) of every validation point of run()
+        if log_steps is not None and int(log_steps) < 1:
+            raise ValueError("log_steps must be >= 1 (or None)")
+        self.log_steps, self.on_log = (int(log_steps) if log_steps is not None else None), on_log
+        self.train_logs = []                # (global_step, dict) of every log_steps-th optimizer step
+        self.meter = None
+        if self.log_steps is not None:
+            from .trainlog import TrainMeter
+            self.meter = TrainMeter(self.meta.names, model._engine.device)
 
     def _step_for(self, task: str, train: bool, batch):
         """The step object that runs `batch`, loaded with it.  reuse_steps: the one capacity step of (task, training / validation), built
@@ -404,7 +418,10 @@ class PretrainDriver:
             raise ValueError(f"unknown task {task!r}: this fork pre-trains with 'mlm' and 'sap' (pretrain_cmt.py:141-163,223-283)")
         loss = st.loss.clone()
         self._micro += 1
-        self.task_losses.setdefault(name, []).append(loss)
+        if self.meter is not None:
+            self.meter.update(name, st)
+        else:
+            self.task_losses.setdefault(name, []).append(loss)
         if self._micro < A:
             self._release(st)
             return loss
@@ -421,8 +438,22 @@ class PretrainDriver:
         self.global_step += 1
         self.lr_history.append(self.sched.step(self.global_step))
         self.opt.step()
+        if self.meter is not None:
+            self._log_point()
         self._release(st)
         return loss
+
+    def _log_point(self) -> None:
+        """behind opt.step() on its stream: the step record; at every log_steps-th optimizer step the one read (train_r2r.py:269-317)"""
+        if self.opt.max_grad_norm > 0.0 or self.opt.check_finite:      # the norm pass ran (opts.grad_norm != -1, :279)
+            self.meter.optimizer_step(self.opt)
+        if self.global_step % self.log_steps:
+            return
+        log = self.meter.read()
+        log["lr"] = self.lr_history[-1]
+        self.train_logs.append((self.global_step, log))
+        if self.on_log is not None:
+            self.on_log(self.global_step, log)
 
     def validate(self, val_loaders: Dict, setname: str = "") -> Dict[str, float]:
         """validate() of train_r2r.py:335-444 (model.eval(): no dropout): for every task of `val_loaders` ({task: batches}) one

@@ -1199,6 +1199,85 @@ int etp_mlm_eval(etp_planner* p, const float* txt_embeds, const uint8_t* txt_mas
 int etp_mlm_stash_logits(const etp_planner* p, int B, int L, int G, int Nm, int64_t* byte_offset, int64_t* ldv);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Pre-training log (pretrain_src/pretrain_src/train_r2r.py:229-317): what the loop tells the user while it trains, as small records
+ * that stay on the device across steps and are read in one copy every log_steps optimizer steps (csrc/trainlog.hip) -- the
+ * training-side twin of etp_eval_record.  Plain vector stores, no atomics of any kind, no scratch; every order of summation is
+ * fixed, so a second run on the same inputs gives the same bits.  Every entry refuses (ETP_ERR_INVALID, nothing launched) NULL
+ * pointers (those marked nullable excepted), misaligned operands and negative counts.
+ * ---------------------------------------------------------------------------------------------------- */
+/* one task's RunningMeter (utils/logger.py:68-94) and its three throughput counters (train_r2r.py:233-234, :246); 64 bytes,
+ * little-endian, 8-byte aligned; starts as all zero bytes */
+typedef struct etp_train_task_record {
+  double run_loss;       /* RunningMeter._val; meaningless while n_values == 0 (the reference's None; .val reports 0) */
+  double last_loss;      /* the value of the last call, taken or not */
+  int64_t n_values;      /* calls whose smoothed value was taken */
+  int64_t n_skipped;     /* calls whose smoothed value was NaN and was dropped (logger.py:80) */
+  int64_t n_examples;    /* n_examples[name] (:233) */
+  int64_t n_in_units;    /* n_in_units[name] (:234): the non-zero bytes of txt_masks, = batch['txt_lens'].sum() */
+  int64_t n_loss_units;  /* n_loss_units[name] (:246): loss.size(0) before the mean */
+  int64_t reserved;
+} etp_train_task_record;
+/* the optimizer steps' gradient norm (train_r2r.py:282-290); 64 bytes; starts as zero bytes with first_nonfinite_step = -1 */
+typedef struct etp_train_step_record {
+  double norm_last;               /* the last step's pre-clip grad_norm, an fp32 value as clip_grad_norm_ returns it */
+  double norm_max;                /* over the finite steps */
+  double norm_sum;                /* over the finite steps, added in double in step order */
+  int64_t n_steps;
+  int64_t n_nonfinite_steps;      /* steps whose norm was not finite or whose non-finite count was not zero */
+  int64_t first_nonfinite_step;   /* the first such step counted from 1 (n_steps after it); -1 = none */
+  int64_t reserved[2];
+} etp_train_step_record;
+/* task2loss[name](loss.item()) of train_r2r.py:259 without the .item(), and the counters of :233-234 and :246.  loss: the step's
+ * device loss (one fp32, already divided by the accumulation steps as :250-252 logs it).  RunningMeter.__call__ (logger.py:77-81)
+ * in Python's double arithmetic, bit for bit: value = (double)*loss; with no value taken yet val = value, otherwise
+ * val = value*(1.0 - smooth) + run_loss*smooth -- 1.0 - smooth formed in double, two double products and one double sum, each rounded
+ * on its own; a NaN val leaves run_loss alone and counts a skip, +-inf is taken.  The counters advance on every call, skipped or not:
+ * n_examples and n_loss_units by the arguments, n_in_units by the number of non-zero bytes among txt_masks[0 .. n_mask_bytes) (the
+ * step's staged bool tensor [B, L]; train_r2r.py:234 sums batch['txt_lens'], which the native batches do not carry).
+ * Refused besides: smooth outside [0, 1).  One workgroup; rec is read and written by this launch alone. */
+int etp_train_meter_loss(const float* loss, double smooth, const uint8_t* txt_masks, int64_t n_mask_bytes, int64_t n_examples,
+                         int64_t n_loss_units, etp_train_task_record* rec, etp_stream_t stream);
+/* grad_norm = clip_grad_norm_(model.parameters(), opts.grad_norm) of train_r2r.py:282-284 and its TB_LOGGER.add_scalar (:290) without
+ * the host read: from the optimizer's sumsq (etp_grad_sqnorm / etp_tensor_report; one fp32) and nonfinite (one int32, nullable = 0),
+ * launched behind the norm pass and before the pair is next zeroed.  grad_norm = (float)sqrt((double)*sumsq), the correctly rounded
+ * fp32 root.  A step whose norm is not finite or whose count is not zero adds to n_nonfinite_steps and not to norm_max / norm_sum.
+ * One thread. */
+int etp_train_meter_step(const float* sumsq, const int32_t* nonfinite, etp_train_step_record* rec, etp_stream_t stream);
+
+/* Per-tensor fingerprint of a float arena: (sum, abs-max, L2) of oracle/make_golden.py:69-73 per tensor -- the per-parameter norm
+ * loop the reference keeps as commented-out debugging code (train_r2r.py:286-289) -- deterministic, in double, without a copy of the
+ * arena to the host.  32 bytes, 8-byte aligned. */
+typedef struct etp_tensor_record {
+  double sum;          /* over the finite values, in double */
+  double sumsq;        /* over the finite values; the square of a float is exact in double, only the additions round */
+  float absmax;        /* over the finite values, exact */
+  int32_t nonfinite;   /* NaN and +-inf values: counted, left out of the three others */
+  int64_t reserved;    /* written as 0 */
+} etp_tensor_record;
+#define ETP_TENSOR_REPORT_CHUNK 16384      /* elements per stage-1 workgroup */
+typedef struct etp_tensor_report_plan etp_tensor_report_plan;
+/* A plan over n_seg segments [seg_off[s], seg_off[s] + seg_len[s]) of an arena of arena_len floats, in elements.  All arrays are HOST
+ * pointers, validated here and uploaded once, at the plan's first etp_tensor_report (creating a plan needs no device).  include
+ * (nullable = all): one byte per segment, non-zero = the segment enters the totals.  The plan owns the per-chunk partials, so one plan
+ * serves one stream at a time.  Refused: n_seg <= 0, arena_len <= 0, an offset that is negative or no multiple of 4, a length < 1,
+ * segments that do not ascend or that overlap, a segment that ends behind arena_len. */
+int etp_tensor_report_create(const int64_t* seg_off, const int64_t* seg_len, const uint8_t* include, int n_seg, int64_t arena_len,
+                             etp_tensor_report_plan** plan);
+/* Host only: the number of stage-1 workgroups, sum over the segments of ceil(seg_len / ETP_TENSOR_REPORT_CHUNK); -1 for NULL. */
+int64_t etp_tensor_report_chunks(const etp_tensor_report_plan* plan);
+/* Three launches on `stream`.  Stage 1: one workgroup of 256 threads per chunk of at most ETP_TENSOR_REPORT_CHUNK elements, never
+ * across a segment (binary search of the chunk prefix); 16-byte loads thread-strided in ascending order, the up to three elements
+ * behind the last whole vector by threads 0 .. 2; the wave's shuffle tree; the four waves in wave order; one partial per chunk.
+ * Stage 2: one wavefront per segment, lane l adds the partials l, l + 64, ... in chunk order, then the shuffle tree; writes
+ * records_out[s].  Stage 3 (when sumsq_out or nonfinite_out is given; both nullable): one wavefront adds the records whose include
+ * byte is non-zero, lane l the segments l, l + 64, ... in segment order, then the shuffle tree, and STORES (float)sum of sumsq and
+ * the int32 non-finite total -- an etp_grad_sqnorm-compatible pair that needs no zeroing; with a non-zero total the float is a
+ * quiet NaN.  Nothing outside the segments is read.  arena 16-byte, records_out 8-byte aligned; records_out [n_seg]. */
+int etp_tensor_report(etp_tensor_report_plan* plan, const float* arena, etp_tensor_record* records_out, float* sumsq_out,
+                      int32_t* nonfinite_out, etp_stream_t stream);
+int etp_tensor_report_destroy(etp_tensor_report_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------
  * hipGraph helpers (launch-bound inner loops are captured once and replayed) and timing.
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct etp_graph etp_graph;
