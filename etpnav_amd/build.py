@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libetpnav_hip.so")
-SOURCES = ["gemm.hip", "gemm_mm32.hip", "attn.hip", "attn_rows.hip", "norm.hip", "embed.hip", "optim.hip", "graph.hip", "decide.hip", "gmap_update.hip", "pano_store.hip", "pano_inputs.hip", "traj_batch.hip", "waypoint.hip", "waypoint_engine.hip", "clip.hip", "clip_engine.hip", "depth.hip", "depth_engine.hip", "eval_tail.hip", "trainlog.hip", "planner.hip", "capi.hip", "graphrec.hip", "comm.hip"]
+SOURCES = ["gemm.hip", "gemm_mm32.hip", "attn.hip", "attn_rows.hip", "norm.hip", "embed.hip", "optim.hip", "graph.hip", "decide.hip", "gmap_update.hip", "pano_store.hip", "pano_inputs.hip", "traj_batch.hip", "waypoint.hip", "waypoint_engine.hip", "clip.hip", "clip_engine.hip", "depth.hip", "depth_engine.hip", "eval_tail.hip", "trainlog.hip", "rollout_loss.hip", "planner.hip", "capi.hip", "graphrec.hip", "comm.hip"]
 HEADERS = ["common.h", "arena.h", "kernels.h", "launch.h", "options.h", "gemm_shared.h", "gemm_tiles.h", "graph_front.h", "row.h", os.path.join("..", "..", "include", "etpnav_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -munsafe-fp-atomics: fp32 atomicAdd lowers to the hardware global_atomic_add_f32 / ds_add_f32 instead of a CAS loop
@@ -29,7 +29,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", 
 # the same source compiled with -fno-slp-vectorize: 0 of 24, with unchanged register counts.  These kernels are HBM- / latency-bound: the
 # packed forms bought nothing measurable.  tools/kernel_resources.py::pk_audit fails the build if one of these objects contains a packed
 # fp32 instruction again.
-NO_PACKED_FP32 = ["embed.hip", "norm.hip", "optim.hip", "graph.hip", "decide.hip", "gmap_update.hip", "pano_store.hip", "pano_inputs.hip", "traj_batch.hip", "waypoint.hip", "clip.hip", "depth.hip", "eval_tail.hip", "trainlog.hip"]
+NO_PACKED_FP32 = ["embed.hip", "norm.hip", "optim.hip", "graph.hip", "decide.hip", "gmap_update.hip", "pano_store.hip", "pano_inputs.hip", "traj_batch.hip", "waypoint.hip", "clip.hip", "depth.hip", "eval_tail.hip", "trainlog.hip", "rollout_loss.hip"]
 PER_SOURCE_FLAGS = {s: ["-fno-slp-vectorize", "-fno-vectorize"] for s in NO_PACKED_FP32}
 # the map update promises numpy's bits: one correctly rounded double operation per step, no fused multiply-add (the file also says so itself)
 PER_SOURCE_FLAGS["gmap_update.hip"] = PER_SOURCE_FLAGS["gmap_update.hip"] + ["-ffp-contract=off"]
@@ -41,6 +41,8 @@ PER_SOURCE_FLAGS["depth.hip"] = PER_SOURCE_FLAGS["depth.hip"] + ["-ffp-contract=
 PER_SOURCE_FLAGS["traj_batch.hip"] = PER_SOURCE_FLAGS["traj_batch.hip"] + ["-ffp-contract=off"]
 # the training meter promises Python's double arithmetic: value*(1 - smooth) + run*smooth, two products and one sum, each rounded
 PER_SOURCE_FLAGS["trainlog.hip"] = PER_SOURCE_FLAGS["trainlog.hip"] + ["-ffp-contract=off"]
+# the rollout loss promises its scale as single rounded double operations: a product and a quotient, then one rounding to fp32
+PER_SOURCE_FLAGS["rollout_loss.hip"] = PER_SOURCE_FLAGS["rollout_loss.hip"] + ["-ffp-contract=off"]
 
 
 def _mtime(p):

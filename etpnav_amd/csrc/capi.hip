@@ -666,6 +666,17 @@ int etp_tensor_report(etp_tensor_report_plan* plan, const float* arena, etp_tens
   return tensor_report(plan, arena, records_out, sumsq_out, nonfinite_out, (hipStream_t)s);
 }
 int etp_tensor_report_destroy(etp_tensor_report_plan* plan) { return tensor_report_destroy(plan); }
+int etp_rollout_ce_fwd(const float* logits, const int64_t* labels, int B, int G, int64_t ignore_index, etp_rollout_record* rec,
+                       float* row_nll, etp_stream_t s) {
+  return rollout_ce_fwd(logits, labels, B, G, (long)ignore_index, rec, row_nll, (hipStream_t)s);
+}
+int etp_rollout_loss(const etp_rollout_record* rec, double ml_weight, float* loss, etp_rollout_log* log, etp_stream_t s) {
+  return rollout_loss(rec, ml_weight, loss, log, (hipStream_t)s);
+}
+int etp_rollout_ce_bwd(const float* logits, const int64_t* labels, int B, int G, int64_t ignore_index, const etp_rollout_record* rec,
+                       double ml_weight, const float* upstream, float* dlogits, etp_stream_t s) {
+  return rollout_ce_bwd(logits, labels, B, G, (long)ignore_index, rec, ml_weight, upstream, dlogits, (hipStream_t)s);
+}
 int etp_gelu_bwd(int dtype, void* d, const void* z, int64_t n, etp_stream_t s) {
   ETP_REQUIRE(dtype == ETP_F32 || dtype == ETP_BF16, "dtype must be ETP_F32 or ETP_BF16");
   ETP_REQUIRE(d && z && n >= 0, "null pointer / negative count");

@@ -82,6 +82,12 @@ long tensor_report_chunks(const etp_tensor_report_plan* p);
 int tensor_report(etp_tensor_report_plan* p, const float* arena, etp_tensor_record* records_out, float* sumsq_out,
                   int32_t* nonfinite_out, hipStream_t st);
 int tensor_report_destroy(etp_tensor_report_plan* p);
+// rollout_loss.hip: the fine-tuning rollout's loss, its scale and its log on the device
+int rollout_ce_fwd(const float* logits, const int64_t* labels, int B, int G, long ignore_index, etp_rollout_record* rec, float* row_nll,
+                   hipStream_t st);
+int rollout_loss(const etp_rollout_record* rec, double ml_weight, float* loss, etp_rollout_log* log, hipStream_t st);
+int rollout_ce_bwd(const float* logits, const int64_t* labels, int B, int G, long ignore_index, const etp_rollout_record* rec,
+                   double ml_weight, const float* upstream, float* dlogits, hipStream_t st);
 int zero_f32(float* dst, long n, hipStream_t st);
 int repeat_block(const void* src, void* dst, long bytes, int T, hipStream_t st);            // dst[t][.] = src[.], t < T
 int sum_steps(int dtype, const void* src, void* dst, long n, int steps, hipStream_t st);   // dst[i] = sum_t src[t][i], fp32 accumulation

@@ -1278,6 +1278,51 @@ int etp_tensor_report(etp_tensor_report_plan* plan, const float* arena, etp_tens
 int etp_tensor_report_destroy(etp_tensor_report_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Fine-tuning rollout loss (vlnce_baselines/ss_trainer_ETP.py:820, :892, :1055-1057): the imitation loss of one rollout, its
+ * scale and the IL_loss log, kept on the device (csrc/rollout_loss.hip).  The divisor total_actions is known only when the last
+ * environment has stopped, so it is no launch argument: the per-step launches advance a device record and the backward launches
+ * read it.  Plain vector stores, no atomics, no scratch; every order of summation is fixed, so a second run on the same inputs gives
+ * the same bits.  PRECONDITION: no NaN in the logits.  Every entry refuses (ETP_ERR_INVALID, nothing launched) NULL pointers (those
+ * marked nullable excepted), B < 1, G < 1, misaligned operands (fp32 4 bytes; labels, record and log 8 bytes) and an output that
+ * overlaps the record.
+ * ---------------------------------------------------------------------------------------------------- */
+/* one rollout's `loss` and `total_actions` (ss_trainer_ETP.py:795-796); 64 bytes, little-endian, 8-byte aligned; starts as zero bytes */
+typedef struct etp_rollout_record {
+  double loss_sum;       /* loss before the scaling of :1055: the rows' nll, added in double in row order, step after step */
+  int64_t n_actions;     /* total_actions (:820): every row handed in, ignored ones included */
+  int64_t n_counted;     /* rows whose label is not ignore_index */
+  int64_t n_steps;       /* etp_rollout_ce_fwd calls */
+  int64_t n_nonfinite;   /* counted rows whose nll is not finite (a label outside [0, G), a label on a -inf logit, a row of only -inf) */
+  int64_t reserved[3];
+} etp_rollout_record;
+/* self.logs['IL_loss'] (:1057) as a running sum: np.mean over an interval is sum / n; 24 bytes, 8-byte aligned; starts as zero bytes */
+typedef struct etp_rollout_log {
+  double sum;            /* the rollouts' fp32 loss values, added in double in call order */
+  int64_t n;             /* values added */
+  int64_t n_nonfinite;   /* values that were not finite (they are added all the same, as np.mean would take them) */
+} etp_rollout_log;
+/* One step: loss += F.cross_entropy(nav_logits, teacher_actions, reduction='sum', ignore_index) (:892) and total_actions += B (:820).
+ * logits fp32 [B, G] with -inf entries, labels [B].  Per row nll = lse - logits[y] with max / sum / lse in etp_sap_eval's order; an
+ * ignored row contributes 0; any other label outside [0, G) gives NaN for its row, adds 1 to n_nonfinite and is never used as an
+ * index.  rec->loss_sum += sum_b (double)nll_b, added in row order by one workgroup; n_actions += B; n_counted += the rows that are
+ * not ignored; n_steps += 1.  The launch loops over the rows, so one call may take T stacked steps as (T*B) rows (n_steps still
+ * advances by 1).  row_nll (nullable) [B] fp32 receives the rows' nll.  rec is read and written by this launch alone. */
+int etp_rollout_ce_fwd(const float* logits, const int64_t* labels, int B, int G, int64_t ignore_index, etp_rollout_record* rec,
+                       float* row_nll /*nullable*/, etp_stream_t stream);
+/* loss = ml_weight * loss / total_actions (:1055): *loss = (float)((ml_weight * loss_sum) / (double)n_actions), the product and the
+ * quotient in double, one rounding to fp32; n_actions == 0 gives exactly 0.  log (nullable): the same fp32 value is added to it --
+ * self.logs['IL_loss'].append(loss.item()) (:1057) without the .item().  Refused besides: loss inside the record, a log that overlaps
+ * either.  One thread. */
+int etp_rollout_loss(const etp_rollout_record* rec, double ml_weight, float* loss, etp_rollout_log* log /*nullable*/,
+                     etp_stream_t stream);
+/* What autograd sends back into one step's nav_logits: dlogits = s * (softmax - onehot) with s = (float)(ml_weight /
+ * (double)rec->n_actions) * *upstream (upstream nullable = 1; n_actions == 0 gives s = 0).  The scale is read from the device, so
+ * total_actions is never copied to the host.  Ignored rows are exactly 0; a -inf logit that no label points at gets exactly 0, as in
+ * etp_sap_ce; a row whose label is neither ignore_index nor a column is NaN.  dlogits fp32 [B, G].  One wavefront per row. */
+int etp_rollout_ce_bwd(const float* logits, const int64_t* labels, int B, int G, int64_t ignore_index, const etp_rollout_record* rec,
+                       double ml_weight, const float* upstream /*nullable: 1*/, float* dlogits, etp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * hipGraph helpers (launch-bound inner loops are captured once and replayed) and timing.
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct etp_graph etp_graph;
